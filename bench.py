@@ -18,7 +18,11 @@ parallel/multi_gpu.py DistributedSuite.plan).  ``gpu`` / ``cpu`` force one
 engine (``cpu``: one single-threaded simulation per core, the reference's
 job-level parallelism).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up (traces, engine placement), warms up, times the K steps
+and prints the result line; ``--dump-outputs DIR`` also writes the last timed
+step's simulated results as DIR/<name>.npy, and ``--full`` adds what the
+headline does not need (the committed hardware cycle correlation).
 Rank 0 prints ONE JSON line.  KIPS = simulated thread instructions (the
 reference's gpu_tot_sim_insn, shader.cc:1911) of all ranks / wall seconds /
 1000; the baseline is the reference's published 349 KIPS (heartwall,
@@ -76,7 +80,37 @@ def _parse():
     # batch of independent simulations per step (parallel/sweep.py)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-configs", type=int, default=16)
-    return ap.parse_args()
+    # after the timed steps: what the last timed step returned, as DIR/<name>.npy
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # everything the result line reports beyond the headline's own run (today:
+    # the committed hardware cycle correlation, cycle_mae_vs_hw)
+    ap.add_argument("--full", action="store_true")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def _dump_outputs(ddir, suite, rank, last):
+    """``--dump-outputs DIR``: the simulated results of the last timed step
+    (what suite.step() / SweepRunner.step() hand their caller, less the wall
+    times and the engine placement, which vary from run to run), float64,
+    one row per rank:
+      totals.npy      [rank] -> (thread instructions, cycles) of the step
+      app_insn.npy    [rank, app] thread instructions of every application
+      app_cycles.npy  [rank, app] simulated cycles of every application
+    Applications in sorted name order (the suite step only)."""
+    import numpy as np
+    mine = {"totals": [float(last["insn"]), float(last["cycles"])]}
+    per = last.get("apps")
+    if per is not None:
+        mine["app_insn"] = [float(per[n]["insn"]) for n in sorted(per)]
+        mine["app_cycles"] = [float(per[n]["cycles"]) for n in sorted(per)]
+    rows = suite.gather(mine)
+    if rank == 0:
+        os.makedirs(ddir, exist_ok=True)
+        for name in mine:
+            np.save(os.path.join(ddir, name + ".npy"), np.asarray([r[name] for r in rows], dtype=np.float64))
 
 
 def _cycle_mae():
@@ -153,6 +187,8 @@ def _sweep(a, suite, engine, rank, world, use_cuda) -> int:
         jobs_cpu += r["jobs_cpu"]
     sync()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, suite, rank, r)
     mine = {"rank": rank, "wall_s": round(dt, 4), "insn": int(insn), "insn_gpu": int(insn_gpu),
             "jobs_gpu": jobs_gpu, "jobs_cpu": jobs_cpu}
     per_rank = suite.gather(mine)
@@ -312,6 +348,8 @@ def main() -> int:
         cycles += r["cycles"]
     sync()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        _dump_outputs(a.dump_outputs, suite, rank, r)
     # max wall time over ranks, total instructions over ranks; the DDP step's
     # simulated cycles: max over ranks (the step ends with the slowest rank)
     dpl = suite.dp_last or {}
@@ -405,7 +443,7 @@ def main() -> int:
             "per_rank": per_rank,
             "plans_identical": plans_identical,
             "wall_s_spread": {"min": min(walls), "max": max(walls)},
-            "cycle_mae_vs_hw": _cycle_mae(),
+            **({"cycle_mae_vs_hw": _cycle_mae()} if a.full else {}),
             "dp_step": ({"ranks": world, "simulated_cycles_max_rank": int(dp_max),
                          "simulated_cycles_per_rank": dp_cycles_per_rank,
                          "collective_mem_traffic": True,

@@ -7,7 +7,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
+# the reference's tested configuration files (gpgpusim.config, trace.config,
+# *.icnt, one AccelWattch xml), stored in the reference tree's own layout
+REFERENCE = os.path.join(ROOT, "tests", "golden", "reference")
 
 
 def pytest_configure(config):
