@@ -495,6 +495,27 @@ PYBIND11_MODULE(_asim, m) {
           return ingest_cmp(k, c, device);
         },
         py::arg("insts"), py::arg("args"), py::arg("device") = 0);
+  // lane policy / register view unit check (csrc/engine/lane_check.h): the
+  // SeqPar result always, the WavePar result when a device is visible
+  m.def("lane_policy_check",
+        [](const std::string& name, int n, const std::vector<uint64_t>& values, const std::vector<uint64_t>& mask) {
+          LaneCheckResult r = lane_policy_check(name, n, values, mask);  // std::invalid_argument -> ValueError
+          py::dict d;
+          d["ran"] = r.ran;
+          d["seq"] = r.seq;
+          d["stat_words"] = r.stat_words;
+          auto bytes_of = [](const std::vector<uint64_t>& v) {
+            return py::bytes(reinterpret_cast<const char*>(v.data()), v.size() * 8);
+          };
+          if (!r.seq_state.empty()) d["seq_state"] = bytes_of(r.seq_state);
+          if (r.ran) {
+            d["wave"] = r.wave;
+            d["stray"] = r.stray;
+            if (!r.wave_state.empty()) d["wave_state"] = bytes_of(r.wave_state);
+          }
+          return d;
+        },
+        py::arg("case"), py::arg("n"), py::arg("values"), py::arg("mask"));
   // host streaming: the per-CTA reader's instructions, accesses and warp
   // streams equal the whole-kernel load's, window by window (CTAs [lo, lo+step)
   // resident, the ones below dropped)

@@ -1567,6 +1567,7 @@ void Simulator::print_sim_time() {
       host_stream_peak_ = std::max(host_stream_peak_, slot_op_[k]->rk->host_peak_bytes);
   if (pwr_in_loop_samples_) print("power_in_loop_samples: %llu\n", (unsigned long long)pwr_in_loop_samples_);
   if (eng_->launches()) print("engine_kernel_launches: %llu\n", (unsigned long long)eng_->launches());
+  if (*eng_->kernel_variant()) print("engine_kernel_variant: %s blocks=%u\n", eng_->kernel_variant(), eng_->kernel_blocks());
   if (host_streamed_)
     print("trace_host_streamed_kernels: %llu\ntrace_host_peak_bytes: %llu\n", (unsigned long long)host_streamed_,
           (unsigned long long)host_stream_peak_);

@@ -94,6 +94,10 @@ class Engine {
   }
   // device kernel launches so far (GPU engine; host engines report 0)
   virtual uint64_t launches() const { return 0; }
+  // which engine kernel build the last launch ran and on how many blocks (GPU
+  // engine; "" / 0 before the first launch and on host engines)
+  virtual const char* kernel_variant() const { return ""; }
+  virtual uint32_t kernel_blocks() const { return 0; }
   // -icnt_link_contention: packets delayed by busy links, their total delay
   // in interconnect cycles (icnt_links.h), and packets a routing deadlock of
   // the router model left at their uncontended latency (icnt_router.h)
@@ -210,6 +214,21 @@ struct EngineKernelInfo {
   bool valid = false;
 };
 EngineKernelInfo gpu_engine_kernel_info();
+
+// Lane-policy check (lane_check.h / lane_check.hip): a named case of the lane
+// policy or of the register view runs under SeqPar on the host and, when a
+// device is visible, under WavePar in a one-wavefront kernel.  Lengths and
+// indices are validated first (std::invalid_argument).  CPU-only builds run
+// the host half (gpu_stub.cc).
+struct LaneCheckResult {
+  std::vector<uint64_t> seq, wave;              // outputs under SeqPar / WavePar
+  std::vector<uint64_t> seq_state, wave_state;  // SM state image after the case (cases on a state)
+  bool ran = false;                             // a device was visible and the kernel ran
+  bool stray = false;  // split state: the kernel wrote the hot part of the HBM image or the tail of the hot copy
+  uint32_t stat_words = (uint32_t)kStatWords;
+};
+LaneCheckResult lane_policy_check(const std::string& name, int n, const std::vector<uint64_t>& values,
+                                  const std::vector<uint64_t>& mask);
 
 // MALL lines of one channel (0 without a MALL)
 inline uint64_t mall_lines(const SimCfg& c) { return (uint64_t)c.mall_sets * c.mall_assoc; }

@@ -831,30 +831,41 @@ class GpuEngine : public Engine {
         sub.nb = nblocks_;
         sub.slots = slots_;
         sub.h_ctl = h_ctl_;
+        variant_ = "batch";
         BatchLauncher::get().run(sub);
         ++launches_;
         HIPCHECK(sub.err);
       } else {
       CuPool::get().acquire((int)(nblocks_ * slots_));
       hipError_t le;
-      if (mode_ == kModeSplit && profiling_)
+      if (mode_ == kModeSplit && profiling_) {
+        variant_ = "split_prof";
         hipLaunchKernelGGL((engine_kernel<WaveParProf, true, kModeSplit>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (mode_ == kModeSplit && split_waves() == 2)
+      } else if (mode_ == kModeSplit && split_waves() == 2) {
+        variant_ = "split2";
         hipLaunchKernelGGL(engine_split2_kernel, dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (mode_ == kModeSplit)
+      } else if (mode_ == kModeSplit) {
+        variant_ = "split";
         hipLaunchKernelGGL((engine_kernel<WavePar, true, kModeSplit>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (global_ && profiling_)
+      } else if (global_ && profiling_) {
+        variant_ = "global_prof";
         hipLaunchKernelGGL((engine_kernel<WaveParProf, true, kModeGlobal>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (global_)
+      } else if (global_) {
+        variant_ = "global";
         hipLaunchKernelGGL((engine_kernel<WavePar, true, kModeGlobal>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (profiling_ && sliced_)
+      } else if (profiling_ && sliced_) {
+        variant_ = "lds_sliced_prof";
         hipLaunchKernelGGL((engine_kernel<WaveParProf, true, kModeLds>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (profiling_)
+      } else if (profiling_) {
+        variant_ = "lds_prof";
         hipLaunchKernelGGL((engine_kernel<WaveParProf, false, kModeLds>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else if (sliced_)
+      } else if (sliced_) {
+        variant_ = "lds_sliced";
         hipLaunchKernelGGL((engine_kernel<WavePar, true, kModeLds>), dim3(nblocks_), dim3(64), lds_, stream_, a);
-      else
+      } else {
+        variant_ = "lds";
         hipLaunchKernelGGL((engine_kernel<WavePar, false, kModeLds>), dim3(nblocks_), dim3(64), lds_, stream_, a);
+      }
       le = hipGetLastError();
       ++launches_;
       hipError_t ce = hipMemcpyAsync(h_ctl_, d_ctl_, sizeof(GpuCtl), hipMemcpyDeviceToHost, stream_);
@@ -1101,6 +1112,8 @@ class GpuEngine : public Engine {
   // in-kernel power sampling (engine.h PwrArm): engine_kernel writes each
   // sample to a device ring, drained after every launch
   uint64_t launches() const override { return launches_; }
+  const char* kernel_variant() const override { return variant_; }
+  uint32_t kernel_blocks() const override { return *variant_ ? nblocks_ : 0; }
   bool power_sampler() const override { return true; }
   void power_arm(const PwrArm& arm) override {
     const uint32_t nunits = c_.n_sm + c_.n_mem;
@@ -1219,6 +1232,7 @@ class GpuEngine : public Engine {
   };
   TraceWindows<DevMem> tw_;
   uint64_t launches_ = 0;
+  const char* variant_ = "";  // engine kernel build of the last launch (diagnostics)
   bool pw_on_ = false;
   PwrDev* d_pw_ = nullptr;
   double* d_pw_rows_ = nullptr;

@@ -1,5 +1,6 @@
 // Linked into CPU-only builds (no HIP engine object).
 #include "engine.h"
+#include "lane_check.h"
 
 namespace asim {
 std::unique_ptr<Engine> make_gpu_engine() { return nullptr; }
@@ -22,4 +23,14 @@ bool gpu_coalesce_kernel(const HostKernel&, const SimCfg&, int, ReadyKernel&, In
 
 namespace asim {
 int gpu_current_device() { return -1; }
+}  // namespace asim
+
+namespace asim {
+// no device: the SeqPar half only (ran stays false)
+LaneCheckResult lane_policy_check(const std::string& name, int n, const std::vector<uint64_t>& values,
+                                  const std::vector<uint64_t>& mask) {
+  LaneCheckResult r;
+  lane_check_host(lane_plan(name, n, values, mask), n, values, mask, r);
+  return r;
+}
 }  // namespace asim
