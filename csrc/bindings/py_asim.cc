@@ -10,6 +10,7 @@
 #include "../config/icnt_config.h"
 #include "../driver/icnt_bench.h"
 #include "../driver/simulator.h"
+#include "../engine/icnt_sweep.h"
 
 namespace py = pybind11;
 using namespace asim;
@@ -144,6 +145,35 @@ py::dict kernel_dict(const KernelResult& k) {
 
 }  // namespace
 
+// an open-loop result as the dict icnt_open_loop returns
+static py::dict open_loop_dict(const OpenLoopResult& r) {
+  py::dict d;
+  d["nodes"] = r.nodes;
+  d["packets"] = r.packets;
+  d["measured_packets"] = r.measured_packets;
+  d["offered"] = r.offered;
+  d["accepted"] = r.accepted;
+  d["drain_throughput"] = r.drain_throughput;
+  d["avg_latency"] = r.avg_latency;
+  d["max_latency"] = r.max_latency;
+  d["zero_load_latency"] = r.zero_load_latency;
+  d["deadlocked"] = r.deadlocked;
+  py::dict a;
+  const char* an[] = {"buffer_writes", "buffer_reads", "link_flits", "eject_flits", "sa_requests", "credits",
+                      "switch_passes"};
+  for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
+  d["activity"] = a;
+  py::dict e;
+  e["buffer"] = r.e_buffer;
+  e["crossbar"] = r.e_xbar;
+  e["link"] = r.e_link;
+  e["allocator"] = r.e_alloc;
+  e["leakage"] = r.e_leak;
+  d["energy_pj"] = e;
+  d["power_w"] = r.power_w;
+  return d;
+}
+
 PYBIND11_MODULE(_asim, m) {
   m.doc() = "MI355X-native trace-driven GPU simulator (native core)";
   m.attr("sizeof_SMState") = sizeof(SMState);
@@ -255,35 +285,64 @@ PYBIND11_MODULE(_asim, m) {
           py::gil_scoped_release nogil;
           r = icnt_open_loop(icnt_text, p);
         }
-        py::dict d;
-        d["nodes"] = r.nodes;
-        d["packets"] = r.packets;
-        d["measured_packets"] = r.measured_packets;
-        d["offered"] = r.offered;
-        d["accepted"] = r.accepted;
-        d["drain_throughput"] = r.drain_throughput;
-        d["avg_latency"] = r.avg_latency;
-        d["max_latency"] = r.max_latency;
-        d["zero_load_latency"] = r.zero_load_latency;
-        d["deadlocked"] = r.deadlocked;
-        py::dict a;
-        const char* an[] = {"buffer_writes", "buffer_reads", "link_flits", "eject_flits", "sa_requests", "credits",
-                            "switch_passes"};
-        for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
-        d["activity"] = a;
-        py::dict e;
-        e["buffer"] = r.e_buffer;
-        e["crossbar"] = r.e_xbar;
-        e["link"] = r.e_link;
-        e["allocator"] = r.e_alloc;
-        e["leakage"] = r.e_leak;
-        d["energy_pj"] = e;
-        d["power_w"] = r.power_w;
-        return d;
+        return open_loop_dict(r);
       },
       py::arg("icnt_text"), py::arg("traffic") = "uniform", py::arg("rate") = 0.1, py::arg("packet_flits") = 1,
       py::arg("cycles") = 2000, py::arg("warmup") = 500, py::arg("seed") = 1,
       "open-loop synthetic traffic through the router model (Booksim standalone mode, icnt_router.h)");
+  m.def(
+      "icnt_open_loop_batch",
+      [](const std::string& icnt_text,
+         const std::vector<std::tuple<std::string, double, uint32_t, uint64_t, uint64_t, uint64_t>>& points,
+         const std::string& engine, bool arrivals, uint64_t mem_budget_mb, uint64_t step_cap, bool lds) {
+        std::vector<OpenLoopParams> ps;
+        for (const auto& t : points) {
+          OpenLoopParams p;
+          p.traffic = std::get<0>(t);
+          p.rate = std::get<1>(t);
+          p.packet_flits = std::get<2>(t);
+          p.cycles = std::get<3>(t);
+          p.warmup = std::get<4>(t);
+          p.seed = std::get<5>(t);
+          ps.push_back(p);
+        }
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<OpenLoopResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_open_loop_batch(icnt_text, ps, engine, o);
+        }
+        py::list out;
+        for (const OpenLoopResult& r : rs) {
+          py::dict d = open_loop_dict(r);
+          if (arrivals) {
+            d["arrivals"] = py::array_t<uint64_t>((py::ssize_t)r.arrivals.size(), r.arrivals.data());
+            d["state"] = py::array_t<uint64_t>((py::ssize_t)r.state.size(), r.state.data());
+          }
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("icnt_text"), py::arg("points"), py::arg("engine") = "cpu", py::arg("arrivals") = false,
+      py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true,
+      "a list of (traffic, rate, packet_flits, cycles, warmup, seed) points through one engine: cpu (rt_simulate), "
+      "cpu-par (the lane-parallel pass on the host) or gpu (one wavefront per point; lds=False keeps the per-VC "
+      "words in HBM); step_cap is for tests");
+  m.def("icnt_open_loop_batch_stats", [] {
+    const OpenLoopBatchStats t = icnt_open_loop_last_batch();
+    py::dict d;
+    d["chunks"] = t.chunks;
+    d["max_chunk_points"] = t.max_chunk_points;
+    d["max_chunk_bytes"] = t.max_chunk_bytes;
+    d["budget_bytes"] = t.budget_bytes;
+    d["lds_chunks"] = t.lds_chunks;
+    return d;
+  }, "how the last gpu batch of this process was packed into launches");
+  m.def("icnt_sweep_kernel_info", &icnt_sweep_kernel_info, "registers, LDS and scratch of the sweep kernel");
   m.def(
       "arch_energy",
       [](const std::vector<std::string>& args, double node_nm, double vdd, double dram_pj_per_bit,

@@ -19,7 +19,10 @@
 #include <vector>
 
 #include "../config/icnt_config.h"
+#include "../engine/engine.h"
+#include "../engine/icnt_sweep.h"
 #include "../model/icnt_router.h"
+#include "../model/icnt_router_par.h"
 
 namespace asim {
 
@@ -189,16 +192,60 @@ AnyNet build_anynet(const std::string& text, uint32_t hop) {
   return a;
 }
 
+// the pass's work arrays over `scratch`, with the point's packets in them
+RtWork load_point(const OpenLoopNet& net, const OpenLoopPoint& pt, std::vector<uint32_t>& scratch) {
+  scratch.assign(rt_carve(pt.d, nullptr, nullptr), 0);
+  RtWork w;
+  rt_carve(pt.d, scratch.data(), &w);
+  if (net.anynet) {
+    w.rt_off = net.rt_off.data();
+    w.rt_links = net.rt_links.data();
+    w.lat = net.lat.data();
+    w.inj_lat = net.inj_lat.data();
+  }
+  for (uint32_t i = 0; i < pt.np; ++i) {
+    w.src[i] = pt.src[i];
+    w.dst[i] = pt.dst[i];
+    w.nfl[i] = pt.pf;
+    w.tinj[i] = pt.tinj[i];
+  }
+  return w;
+}
+
+// the router pass of one point on the host: rt_simulate, or the lane-parallel
+// pass under the sequential lane policy
+OpenLoopRaw simulate_host(const OpenLoopNet& net, const OpenLoopPoint& pt, bool par, uint64_t step_cap) {
+  OpenLoopRaw raw;
+  raw.state.assign(rt_state_words(pt.d), 0);
+  std::vector<uint32_t> scratch;
+  const RtWork w = load_point(net, pt, scratch);
+  if (pt.np) {
+    raw.deadlocked = par ? rt_simulate_par<SeqPar>(net.c, pt.d, raw.state.data(), w, pt.np, raw.act, &raw.status, step_cap)
+                         : rt_simulate(net.c, pt.d, raw.state.data(), w, pt.np, raw.act);
+  }
+  raw.tarr.assign(w.tarr, w.tarr + pt.np);
+  return raw;
+}
+
+OpenLoopBatchStats g_last;  // of the last batch call (one caller at a time)
+
+void check_status(const OpenLoopRaw& raw, size_t index) {
+  if (raw.status != RT_STATUS_OK)
+    throw std::runtime_error("icnt_open_loop_batch: point " + std::to_string(index) +
+                             ": the router pass exceeded its step cap (loop guard)");
+}
+
 }  // namespace
 
-OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams& prm) {
-  SimCfg c{};
+OpenLoopNet icnt_open_loop_net(const std::string& icnt_text) {
+  OpenLoopNet net;
+  SimCfg& c = net.c;
   c.flit_size = 32;
-  const auto kv = parse_booksim_config(icnt_text);
-  const bool anynet = kv.count("topology") && kv.at("topology") == "anynet";
-  AnyNet an;
+  net.kv = parse_booksim_config(icnt_text);
+  const auto& kv = net.kv;
+  net.anynet = kv.count("topology") && kv.at("topology") == "anynet";
   uint64_t nodes = 0;
-  if (anynet) {
+  if (net.anynet) {
     // the router microarchitecture and pipeline from the file, the network
     // from its network_file
     auto k2 = kv;
@@ -211,22 +258,38 @@ OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams
     if (!f.good()) throw std::invalid_argument("cannot open anynet network_file '" + kv.at("network_file") + "'");
     std::stringstream ss;
     ss << f.rdbuf();
-    an = build_anynet(ss.str(), c.hop_icnt);
+    AnyNet an = build_anynet(ss.str(), c.hop_icnt);
     nodes = an.N;
+    net.an_L = (uint32_t)an.lat.size();
+    net.an_H = an.H;
+    net.rt_off = std::move(an.off);
+    net.rt_links = std::move(an.route);
+    net.lat = std::move(an.lat);
+    net.inj_lat = std::move(an.inj_lat);
   } else {
     nodes = apply_topology(c, kv);
   }
   if (c.rt_alloc == 0xff) throw std::invalid_argument("sw_allocator not modelled");
   c.link_contention = 2;
   if (nodes > (1u << 20)) throw std::invalid_argument("topology too large");
-  const uint32_t N = (uint32_t)nodes;
+  net.N = (uint32_t)nodes;
+  return net;
+}
+
+OpenLoopPoint icnt_open_loop_prepare(const OpenLoopNet& net, const OpenLoopParams& prm) {
+  const SimCfg& c = net.c;
+  const uint32_t N = net.N;
+  const bool anynet = net.anynet;
+  OpenLoopPoint pt;
+  pt.prm = prm;
   const uint32_t pf = prm.packet_flits ? prm.packet_flits : 1;
+  pt.pf = pf;
   if (prm.rate < 0 || prm.rate > 1) throw std::invalid_argument("rate must be 0..1 flits per node per cycle");
   if (prm.warmup >= prm.cycles) throw std::invalid_argument("warmup must be shorter than the run");
   // the injection schedule
   Rng r{prm.seed * 0x2545f4914f6cdd1dull + 1};
-  std::vector<uint32_t> src, dst;
-  std::vector<uint64_t> tinj;
+  std::vector<uint32_t>&src = pt.src, &dst = pt.dst;
+  std::vector<uint64_t>& tinj = pt.tinj;
   const double p_pkt = prm.rate / pf;
   for (uint64_t t = 0; t < prm.cycles; ++t)
     for (uint32_t s = 0; s < N; ++s)
@@ -240,48 +303,46 @@ OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams
   const uint64_t np64 = src.size();
   if (np64 > 50'000'000ull) throw std::invalid_argument("too many packets for one pass");
   const uint32_t np = (uint32_t)np64;
+  pt.np = np;
   RtDims d = rt_dims(c, np ? np : 1, pf);
   if (anynet) {
-    d.N = an.N;
-    d.L = (uint32_t)an.lat.size();
+    d.N = N;
+    d.L = net.an_L;
     d.U = d.N + d.L;
-    d.H = an.H;
+    d.H = net.an_H;
   }
-  std::vector<uint64_t> st(rt_state_words(d), 0);
-  std::vector<uint32_t> scratch(rt_carve(d, nullptr, nullptr), 0);
-  RtWork w;
-  rt_carve(d, scratch.data(), &w);
-  if (anynet) {
-    w.rt_off = an.off.data();
-    w.rt_links = an.route.data();
-    w.lat = an.lat.data();
-    w.inj_lat = an.inj_lat.data();
-  }
-  for (uint32_t i = 0; i < np; ++i) {
-    w.src[i] = src[i];
-    w.dst[i] = dst[i];
-    w.nfl[i] = pf;
-    w.tinj[i] = tinj[i];
-  }
+  pt.d = d;
+  return pt;
+}
+
+OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPoint& pt, const OpenLoopRaw& raw) {
+  const SimCfg& c = net.c;
+  const auto& kv = net.kv;
+  const OpenLoopParams& prm = pt.prm;
+  const bool anynet = net.anynet;
+  const uint32_t N = net.N, np = pt.np, pf = pt.pf;
+  const RtDims& d = pt.d;
+  const std::vector<uint32_t>&src = pt.src, &dst = pt.dst;
+  const std::vector<uint64_t>& tinj = pt.tinj;
+  const uint64_t* act = raw.act;
   OpenLoopResult res;
   res.nodes = N;
   res.packets = np;
-  uint64_t act[RT_ACT_COUNT] = {};
-  res.deadlocked = np ? rt_simulate(c, d, st.data(), w, np, act) : 0;
+  res.deadlocked = raw.deadlocked;
   for (int i = 0; i < RT_ACT_COUNT; ++i) res.activity[i] = act[i];
   double lat = 0, zero = 0;
   uint64_t meas = 0, ejected = 0, last = 0;
   for (uint32_t i = 0; i < np; ++i) {
-    const uint64_t a = w.tarr[i];
+    const uint64_t a = raw.tarr[i];
     last = std::max(last, a);
     if (a >= prm.warmup && a < prm.cycles) ejected += pf;
     if (tinj[i] >= prm.warmup) {
       lat += (double)(a - tinj[i]);
       if (anynet) {
         // injection channel + per router its delay and its output channel
-        uint64_t z = an.inj_lat[src[i]] + (pf - 1);
-        const size_t pr = (size_t)src[i] * an.N + dst[i];
-        for (uint32_t k = an.off[pr]; k < an.off[pr + 1]; ++k) z += c.hop_icnt + an.lat[an.route[k]];
+        uint64_t z = net.inj_lat[src[i]] + (pf - 1);
+        const size_t pr = (size_t)src[i] * N + dst[i];
+        for (uint32_t k = net.rt_off[pr]; k < net.rt_off[pr + 1]; ++k) z += c.hop_icnt + net.lat[net.rt_links[k]];
         zero += (double)z;
       } else {
         zero += (double)rt_uncontended(c, icnt_routers(c, src[i], dst[i]), pf);
@@ -320,4 +381,73 @@ OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams
   return res;
 }
 
+OpenLoopBatchStats icnt_open_loop_last_batch() { return g_last; }
+
+OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams& prm) {
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  const OpenLoopPoint pt = icnt_open_loop_prepare(net, prm);
+  return icnt_open_loop_summarise(net, pt, simulate_host(net, pt, false, 0));
+}
+
+std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
+                                                 const std::vector<OpenLoopParams>& points,
+                                                 const std::string& engine, const OpenLoopBatchOpts& opts) {
+  if (engine != "cpu" && engine != "cpu-par" && engine != "gpu")
+    throw std::invalid_argument("icnt_open_loop_batch: engine must be cpu, cpu-par or gpu, not '" + engine + "'");
+  if (engine == "gpu" && !gpu_engine_available())
+    throw std::runtime_error("icnt_open_loop_batch: engine 'gpu' needs a HIP device, and none is usable");
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  std::vector<OpenLoopResult> out;
+  out.reserve(points.size());
+  auto finish = [&](const OpenLoopPoint& pt, OpenLoopRaw& raw) {
+    check_status(raw, out.size());
+    OpenLoopResult r = icnt_open_loop_summarise(net, pt, raw);
+    if (opts.arrivals) {
+      r.arrivals = std::move(raw.tarr);
+      r.state = std::move(raw.state);
+    }
+    out.push_back(std::move(r));
+  };
+  g_last = OpenLoopBatchStats();
+  if (engine != "gpu") {
+    for (const OpenLoopParams& p : points) {
+      const OpenLoopPoint pt = icnt_open_loop_prepare(net, p);
+      OpenLoopRaw raw = simulate_host(net, pt, engine == "cpu-par", opts.step_cap);
+      finish(pt, raw);
+    }
+    return out;
+  }
+  // gpu: points are prepared one after the other and packed into chunks
+  // under the memory budget; a full chunk is launched, summarised and dropped
+  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb);
+  g_last.budget_bytes = budget;
+  std::vector<OpenLoopPoint> chunk;
+  uint64_t used = 0;
+  auto flush = [&] {
+    if (chunk.empty()) return;
+    std::vector<OpenLoopRaw> raws;
+    if (icnt_sweep_run_chunk(net, chunk, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
+    ++g_last.chunks;
+    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
+    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
+    for (size_t i = 0; i < chunk.size(); ++i) finish(chunk[i], raws[i]);
+    chunk.clear();
+    used = 0;
+  };
+  for (size_t i = 0; i < points.size(); ++i) {
+    OpenLoopPoint pt = icnt_open_loop_prepare(net, points[i]);
+    const uint64_t need = icnt_sweep_point_bytes(pt);
+    if (need > budget)
+      throw std::invalid_argument("icnt_open_loop_batch: point " + std::to_string(i) + " needs " +
+                                  std::to_string((need + (1u << 20) - 1) >> 20) + " MB, the memory budget is " +
+                                  std::to_string(budget >> 20) + " MB");
+    if (used + need > budget) flush();
+    used += need;
+    chunk.push_back(std::move(pt));
+  }
+  flush();
+  return out;
+}
+
 }  // namespace asim
+

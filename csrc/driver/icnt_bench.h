@@ -1,7 +1,12 @@
 // Open-loop synthetic traffic through the router model (icnt_bench.cc).
 #pragma once
 #include <cstdint>
+#include <map>
 #include <string>
+#include <vector>
+
+#include "../model/config.h"
+#include "../model/icnt_router.h"
 
 namespace asim {
 
@@ -26,10 +31,71 @@ struct OpenLoopResult {
   // .icnt file's power_* keys), pJ, and the average network power, W
   uint64_t activity[8] = {};
   double e_buffer = 0, e_xbar = 0, e_link = 0, e_alloc = 0, e_leak = 0, power_w = 0;
+  // on request (icnt_open_loop_batch): every packet's arrival and the final state words of the pass
+  std::vector<uint64_t> arrivals, state;
 };
 
 // icnt_text: a Booksim .icnt file's text (topology, router pipeline and
 // microarchitecture keys)
 OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams& p);
+
+// ---- the three steps of a run: prepare, simulate, summarise ----
+
+// the network of an .icnt file: the router configuration and, for anynet, the
+// explicit route and latency tables (empty otherwise)
+struct OpenLoopNet {
+  SimCfg c{};
+  std::map<std::string, std::string> kv;
+  bool anynet = false;
+  uint32_t N = 0;           // nodes
+  uint32_t an_L = 0, an_H = 1;  // anynet: links and longest route
+  std::vector<uint32_t> rt_off, rt_links;
+  std::vector<uint16_t> lat, inj_lat;
+};
+
+// one point's injection schedule and pass dimensions
+struct OpenLoopPoint {
+  OpenLoopParams prm;
+  uint32_t pf = 1, np = 0;
+  RtDims d{};
+  std::vector<uint32_t> src, dst;
+  std::vector<uint64_t> tinj;
+};
+
+// what a router pass leaves
+struct OpenLoopRaw {
+  std::vector<uint64_t> tarr, state;
+  uint64_t act[RT_ACT_COUNT] = {};
+  uint32_t deadlocked = 0;
+  uint32_t status = 0;  // icnt_router_par.h RtStatus
+};
+
+OpenLoopNet icnt_open_loop_net(const std::string& icnt_text);
+OpenLoopPoint icnt_open_loop_prepare(const OpenLoopNet& net, const OpenLoopParams& p);
+OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPoint& pt, const OpenLoopRaw& raw);
+
+struct OpenLoopBatchOpts {
+  bool arrivals = false;       // keep arrivals and state in every result
+  uint64_t mem_budget_mb = 0;  // gpu: device memory of one chunk (0: from the free device memory)
+  uint64_t step_cap = 0;       // tests only: the loop guard's cap (cpu-par and gpu; 0: rt_step_cap)
+  bool lds = true;             // gpu: the per-(unit, VC) words in LDS when they fit (false: always HBM)
+};
+
+// how the last gpu batch of this process was packed
+struct OpenLoopBatchStats {
+  uint64_t chunks = 0, max_chunk_points = 0, max_chunk_bytes = 0, budget_bytes = 0;
+  uint64_t lds_chunks = 0;  // launches with the per-(unit, VC) words in LDS
+};
+OpenLoopBatchStats icnt_open_loop_last_batch();
+
+// every point of `points` through one engine: "cpu" (rt_simulate), "cpu-par"
+// (rt_simulate_par<SeqPar>) or "gpu" (engine/icnt_sweep.hip, one wavefront
+// per point).  One result per point, in order.  std::invalid_argument: a bad
+// point or engine name, or a point larger than the memory budget;
+// std::runtime_error: no usable device, or a pass cut off by its loop guard.
+std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
+                                                 const std::vector<OpenLoopParams>& points,
+                                                 const std::string& engine = "cpu",
+                                                 const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
 
 }  // namespace asim

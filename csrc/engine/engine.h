@@ -204,6 +204,10 @@ int gpu_cu_count();  // compute units of the current HIP device (0 if none)
 int gpu_cus_per_sim(uint32_t n_sm, uint32_t n_mem);  // CUs one GPU-engine simulation of this shape reserves
 std::map<std::string, uint64_t> gpu_pool_stats();  // the GPU engine's caching allocator (empty without HIP)
 void gpu_pool_trim();  // give the allocator's cached blocks back to the driver
+// a device block from / back to that allocator, for the process's other GPU
+// work (engine/icnt_sweep.hip); std::runtime_error when the device has none
+void* gpu_pool_alloc(size_t bytes);
+void gpu_pool_release(void* p);
 std::map<std::string, uint64_t> gpu_batch_stats();
 std::map<std::string, std::map<std::string, uint64_t>> gpu_engine_modes();  // per engine build: LDS, blocks per CU, registers  // global-state batch launches: batches, launches, blocks per CU
 // compiled resources of the persistent engine kernel (empty if no HIP build):

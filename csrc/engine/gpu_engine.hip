@@ -1364,6 +1364,8 @@ std::map<std::string, uint64_t> gpu_pool_stats() {
           {"cap_host", t.cap_host}, {"trims", t.trims}, {"freed_over_cap", t.freed_over_cap}};
 }
 void gpu_pool_trim() { DevicePool::get().trim(); }
+void* gpu_pool_alloc(size_t bytes) { return DevicePool::get().dev(bytes); }
+void gpu_pool_release(void* p) { DevicePool::get().dev_free(p); }
 // per engine build: LDS bytes per block, blocks per CU (occupancy API less
 // the margin), registers and scratch of its kernel
 std::map<std::string, std::map<std::string, uint64_t>> gpu_engine_modes() {

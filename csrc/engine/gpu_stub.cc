@@ -1,6 +1,9 @@
 // Linked into CPU-only builds (no HIP engine object).
+#include <stdexcept>
+
 #include "engine.h"
 #include "lane_check.h"
+#include "icnt_sweep.h"
 
 namespace asim {
 std::unique_ptr<Engine> make_gpu_engine() { return nullptr; }
@@ -12,6 +15,8 @@ int gpu_cu_count() { return 0; }
 int gpu_cus_per_sim(uint32_t n_sm, uint32_t n_mem) { return (int)(n_sm + n_mem); }
 std::map<std::string, uint64_t> gpu_pool_stats() { return {}; }
 void gpu_pool_trim() {}
+void* gpu_pool_alloc(size_t) { throw std::runtime_error("no GPU engine in this build"); }
+void gpu_pool_release(void*) {}
 std::map<std::string, uint64_t> gpu_batch_stats() { return {}; }
 std::map<std::string, std::map<std::string, uint64_t>> gpu_engine_modes() { return {}; }
 EngineKernelInfo gpu_engine_kernel_info() { return EngineKernelInfo{}; }
@@ -33,4 +38,15 @@ LaneCheckResult lane_policy_check(const std::string& name, int n, const std::vec
   lane_check_host(lane_plan(name, n, values, mask), n, values, mask, r);
   return r;
 }
+}  // namespace asim
+
+namespace asim {
+// no device: the batch entry point refuses engine "gpu" before it gets here
+uint64_t icnt_sweep_point_bytes(const OpenLoopPoint&) { return 0; }
+uint64_t icnt_sweep_budget_bytes(uint64_t) { throw std::runtime_error("no GPU engine in this build"); }
+bool icnt_sweep_run_chunk(const OpenLoopNet&, const std::vector<OpenLoopPoint>&, uint64_t, bool,
+                          std::vector<OpenLoopRaw>&) {
+  throw std::runtime_error("no GPU engine in this build");
+}
+std::map<std::string, uint64_t> icnt_sweep_kernel_info() { return {}; }
 }  // namespace asim

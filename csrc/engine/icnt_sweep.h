@@ -1,0 +1,40 @@
+// Open-loop network sweeps on the GPU (icnt_sweep.hip): one 64-lane
+// wavefront per sweep point runs the lane-parallel router pass
+// (model/icnt_router_par.h) on that point's scratch in HBM.  The caller
+// (driver/icnt_bench.cc icnt_open_loop_batch) packs the points into chunks
+// under a memory budget; one chunk is one launch.  Host-only builds link the
+// stub in gpu_stub.cc.
+#pragma once
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../driver/icnt_bench.h"
+
+namespace asim {
+
+// device bytes a point takes in a chunk (scratch, state, results)
+uint64_t icnt_sweep_point_bytes(const OpenLoopPoint& pt);
+
+// bytes of one chunk: mem_budget_mb, or kIcntSweepFreeShare of the free
+// device memory when it is 0
+constexpr double kIcntSweepFreeShare = 0.5;  // the rest is left to the process's other engines
+uint64_t icnt_sweep_budget_bytes(uint64_t mem_budget_mb);
+
+// the per-(unit, VC) words of a pass go to LDS when they fit this much (the
+// default dynamic LDS limit of a launch; an 8x8 mesh with 2 VCs takes 15 KB)
+constexpr uint64_t kIcntSweepLdsBytes = 48 * 1024;
+
+// one launch: grid = the chunk's points, 64 lanes each.  raws[i] is point
+// i's arrivals, final state, activity, deadlocked packets and guard status.
+// allow_lds false keeps the per-(unit, VC) words in HBM; returns whether
+// they were in LDS.
+bool icnt_sweep_run_chunk(const OpenLoopNet& net, const std::vector<OpenLoopPoint>& pts, uint64_t step_cap,
+                          bool allow_lds, std::vector<OpenLoopRaw>& raws);
+
+// registers, LDS and scratch of the kernel (code-object metadata through the
+// HIP function attributes); empty without a device
+std::map<std::string, uint64_t> icnt_sweep_kernel_info();
+
+}  // namespace asim

@@ -25,7 +25,7 @@ namespace asim {
 enum LaneCase : int {
   LC_BALLOT = 0, LC_BALLOT_M, LC_EACH_M, LC_RED_SUM, LC_RED_OR, LC_SUM, LC_VMAX, LC_VOR, LC_RED_SUM64, LC_RED_MIN64,
   LC_RED_MAX64, LC_ARGMIN, LC_FIND_FIRST, LC_SCAN, LC_ORDER16, LC_LANES, LC_UNI, LC_FETCH, LC_REG, LC_SB, LC_STAT,
-  LC_VIEW
+  LC_VIEW, LC_MIN32
 };
 
 constexpr int kLaneScratch = 1024;   // bytes of scratch (LDS and HBM) a case may use
@@ -276,6 +276,14 @@ SIM_HD void lane_case_prim(const LaneArgs& a) {
       if (a.sub == 16) lane_fetch_case<P, LaneB16>(a);
       else lane_fetch_case<P, LaneB32>(a);
       break;
+    case LC_MIN32: {
+      // value i goes into slot m[i] (64 slots, the low words of out[0..64))
+      P::each(64, [&](int i) { a.out[i] = 0xffffffffull; });
+      P::sync();
+      P::each(n, [&](int i) { P::min32(reinterpret_cast<uint32_t*>(a.out + a.m[i]), (uint32_t)v[i]); });
+      P::sync();
+      break;
+    }
     case LC_REG:
       if ((a.sub & 3) == 0) lane_reg_types<P, 16>(a);
       else if ((a.sub & 3) == 1) lane_reg_types<P, 48>(a);
@@ -479,6 +487,13 @@ inline LanePlan lane_plan(const std::string& name, int n, const std::vector<uint
       }
       return p;
     }
+  if (name == "min32") {
+    need(n >= 0 && n <= kLaneMaxN && nv >= (size_t)n && nm >= (size_t)n, "n values and n slots, n <= 4096");
+    for (int i = 0; i < n; ++i) need(m[i] < 64, "slot below 64");
+    p.id = LC_MIN32;
+    p.nout = 64;
+    return p;
+  }
   auto tail_int = [&](const std::string& prefix) -> int {
     if (name.compare(0, prefix.size(), prefix) != 0) return -1;
     const std::string t = name.substr(prefix.size());

@@ -302,6 +302,11 @@ struct WavePar {
     const uint32_t lo = wave_reduce((uint32_t)s, o), hi = wave_reduce((uint32_t)(s >> 32), o);
     return ((uint64_t)hi << 32) | lo;
   }
+  // order-free minimum into one word from several lanes (hd.h SeqPar::min32):
+  // the memory system's atomic, relaxed; readers come after a sync()
+  static __device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
+    (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
   // exclusive scan: within-row Hillis-Steele on row_shr:1/2/4/8 (lanes
   // shifted in from outside the row read 0), then the row totals via readlane
   template <class F, class G>

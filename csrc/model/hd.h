@@ -180,6 +180,12 @@ struct SeqPar {
     for (int i = 0; i < n; ++i) s |= f(i);
     return s;
   }
+  // *p = min(*p, v) from inside lane-parallel code (each / lane_loop bodies),
+  // several lanes on one word: a minimum does not depend on the order, so the
+  // word ends up the same under every policy.  Readers come after a sync().
+  static SIM_HDI void min32(uint32_t* p, uint32_t v) {
+    if (v < *p) *p = v;
+  }
   // the members of `mask` (indices < n <= 16) sorted by key ascending (ties
   // to the lower index), packed 4 bits per entry: entry r = (ord >> 4r) & 15.
   // Replaces repeated "oldest remaining" argmin scans with one ranking.

@@ -1,0 +1,340 @@
+"""The lane-parallel router pass and the batched open-loop sweep.
+
+Every comparison is on the full per-point tuple against the sequential host
+pass (engine ``cpu``): the arrivals array, the deadlocked count, all seven
+activity counters, the final state words and the whole result dict.  The CPU
+tests check ``cpu-par`` (rt_simulate_par<SeqPar>), the ``gpu``-marked ones the
+device kernel (rt_simulate_par<WavePar>, one wavefront per point).  All
+points of a case go into one batch call.
+"""
+import json
+import random
+
+import numpy as np
+import pytest
+
+from accel_sim_framework_distributed_amd.models import presets
+
+CYC, WARM = 300, 50
+
+
+def _icnt(**kw):
+    base = dict(vc_buf_size="8", internal_speedup="1.0")
+    base.update(kw)
+    return presets.render_icnt(presets.icnt_params(**base))
+
+
+def _pt(traffic="uniform", rate=0.5, flits=1, seed=1, cycles=CYC, warmup=WARM):
+    return (traffic, rate, flits, cycles, warmup, seed)
+
+
+MESH = dict(k=4, n=2, topology="mesh")
+TORUS = dict(k=4, n=2, topology="torus")
+ALLOCATORS = ("islip", "separable_input_first", "separable_output_first", "wavefront", "max_size", "pim", "loa")
+
+# name -> (icnt keys, points)
+CASES = {
+    "credits_wormhole": (dict(MESH, num_vcs=2, vc_buf_size=2), [_pt(rate=0.6, flits=4)]),
+    "starved_buffers": (dict(MESH, num_vcs=1, vc_buf_size=1, credit_delay=2), [_pt(rate=1.0, flits=3)]),
+    "speedup": (dict(k=8, n=1, num_vcs=2, internal_speedup="2.0", alloc_iters=2), [_pt(rate=0.9), _pt(rate=0.5, seed=2)]),
+    "speedup_fractional": (dict(k=8, n=1, num_vcs=2, internal_speedup="1.5", alloc_iters=2),
+                           [_pt(rate=0.9, flits=2), _pt(rate=0.5, flits=2, seed=2)]),
+    "multi_stage": (dict(k=2, n=3), [_pt(rate=0.8, flits=2)]),
+    "dateline": (dict(TORUS, num_vcs=2, vc_buf_size=2), [_pt("tornado", 0.8, 2)]),
+    "deadlock": (dict(TORUS, num_vcs=1), [_pt(rate=1.0, flits=1)]),
+    "min_adapt": (dict(MESH, num_vcs=3, vc_buf_size=2, routing_function="min_adapt"), [_pt("transpose", 1.0, 2)]),
+    "valiant": (dict(MESH, num_vcs=4, vc_buf_size=2, routing_function="valiant"), [_pt(rate=0.8, flits=2)]),
+    "cmesh": (dict(k=2, n=2, c=4, topology="cmesh", num_vcs=2), [_pt(rate=0.5, flits=2)]),
+    "fattree": (dict(k=2, n=3, topology="fattree", num_vcs=2), [_pt(rate=0.5, flits=2)]),
+    "flatfly": (dict(k=4, n=2, c=1, topology="flatfly", num_vcs=2), [_pt(rate=0.5, flits=2)]),
+}
+for _a in ALLOCATORS:
+    CASES["alloc_" + _a] = (dict(MESH, num_vcs=2, vc_buf_size=2, alloc_iters=2, sw_allocator=_a),
+                            [_pt(rate=0.8, flits=2, seed=3)])
+
+# a rate-0 point (no packets) between two non-empty ones, then enough points for several chunks
+MECH_KEYS = dict(MESH, num_vcs=2, vc_buf_size=2)
+MECH_POINTS = [_pt(rate=0.6, flits=4), _pt(rate=0.0), _pt(rate=0.3, flits=2, seed=2)] + \
+              [_pt(rate=0.6, flits=4, seed=s) for s in range(3, 9)]
+
+_ref = {}
+
+
+@pytest.fixture(scope="module")
+def gpu_native():
+    import torch  # bind torch's HIP runtime first
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test run without a visible GPU")
+    from accel_sim_framework_distributed_amd import _native
+    mod = _native.load(prefer_torch_runtime=True)
+    assert mod.gpu_available(), "HIP device not usable (native code must run, no silent fallback)"
+    return mod
+
+
+def _batch(native, text, points, engine, **kw):
+    return native.icnt_open_loop_batch(text, points, engine=engine, arrivals=True, **kw)
+
+
+def _reference(native, key, text, points):
+    """The sequential host pass of a case, computed once and left unchanged."""
+    if key not in _ref:
+        _ref[key] = _batch(native, text, points, "cpu")
+    return _ref[key]
+
+
+def _same(got, ref):
+    assert len(got) == len(ref)
+    for i, (g, r) in enumerate(zip(got, ref)):
+        assert np.array_equal(g["arrivals"], r["arrivals"]), f"point {i}: arrivals"
+        assert g["arrivals"].dtype == np.uint64 and g["state"].dtype == np.uint64
+        assert g["deadlocked"] == r["deadlocked"], f"point {i}: deadlocked"
+        assert len(g["activity"]) == 7 and g["activity"] == r["activity"], f"point {i}: activity"
+        assert np.array_equal(g["state"], r["state"]), f"point {i}: state"
+        gd = {k: v for k, v in g.items() if k not in ("arrivals", "state")}
+        rd = {k: v for k, v in r.items() if k not in ("arrivals", "state")}
+        assert gd == rd, f"point {i}: result"
+
+
+def _check_case(native, name, engine):
+    keys, points = CASES[name]
+    text = _icnt(**keys)
+    ref = _reference(native, name, text, points)
+    assert all(r["packets"] > 0 for r in ref)
+    if name == "deadlock":
+        assert ref[0]["deadlocked"] > 0
+    _same(_batch(native, text, points, engine), ref)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_cpu_par_equals_cpu(native, name):
+    _check_case(native, name, "cpu-par")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_gpu_equals_cpu(gpu_native, name):
+    _check_case(gpu_native, name, "gpu")
+
+
+def _anynet(tmp_path):
+    """The 4 x 4 mesh network file of test_router_anynet_network_file, and its
+    pair of routers joined by a 5-cycle channel."""
+    k = 4
+    lines = []
+    for y in range(k):
+        for x in range(k):
+            r = y * k + x
+            parts = [f"router {r}", f"node {r}"]
+            if x + 1 < k:
+                parts.append(f"router {r + 1}")
+            if y + 1 < k:
+                parts.append(f"router {r + k}")
+            lines.append(" ".join(parts))
+    f = tmp_path / "mesh44.anynet"
+    f.write_text("\n".join(lines) + "\n")
+    g = tmp_path / "pair.anynet"
+    g.write_text("router 0 node 0 router 1 5\nrouter 1 node 1\n")
+    return [(_icnt(k=4, topology="anynet", network_file=str(f), num_vcs=2, vc_buf_size=2),
+             [_pt(rate=0.6, flits=2), _pt(rate=0.2, seed=2)]),
+            (_icnt(k=2, topology="anynet", network_file=str(g)), [_pt(rate=0.5, flits=2)])]
+
+
+def _check_anynet(native, tmp_path, engine):
+    for text, points in _anynet(tmp_path):
+        ref = _batch(native, text, points, "cpu")
+        assert all(r["packets"] > 0 for r in ref)
+        _same(_batch(native, text, points, engine), ref)
+
+
+def test_cpu_par_anynet(native, tmp_path):
+    _check_anynet(native, tmp_path, "cpu-par")
+
+
+@pytest.mark.gpu
+def test_gpu_anynet(gpu_native, tmp_path):
+    _check_anynet(gpu_native, tmp_path, "gpu")
+
+
+def test_cpu_par_batch_mechanics(native):
+    text = _icnt(**MECH_KEYS)
+    ref = _reference(native, "mech", text, MECH_POINTS)
+    assert ref[1]["packets"] == 0 and ref[0]["packets"] > 0 and ref[2]["packets"] > 0
+    assert len(ref[1]["arrivals"]) == 0
+    _same(_batch(native, text, MECH_POINTS, "cpu-par"), ref)
+
+
+@pytest.mark.gpu
+def test_gpu_batch_mechanics_and_chunks(gpu_native):
+    text = _icnt(**MECH_KEYS)
+    ref = _reference(gpu_native, "mech", text, MECH_POINTS)
+    _same(_batch(gpu_native, text, MECH_POINTS, "gpu"), ref)
+    one = gpu_native.icnt_open_loop_batch_stats()
+    assert one["chunks"] == 1 and one["max_chunk_points"] == len(MECH_POINTS) and one["lds_chunks"] == 1
+    # a 1 MB budget holds a few of these points: several launches, the same list
+    _same(_batch(gpu_native, text, MECH_POINTS, "gpu", mem_budget_mb=1), ref)
+    st = gpu_native.icnt_open_loop_batch_stats()
+    assert st["chunks"] >= 3 and st["max_chunk_bytes"] <= 1 << 20
+    # a point that alone exceeds the budget
+    big = [_pt(rate=1.0, flits=4, cycles=3000, warmup=50)]
+    with pytest.raises(ValueError, match="memory budget"):
+        gpu_native.icnt_open_loop_batch(text, big, engine="gpu", mem_budget_mb=1)
+
+
+@pytest.mark.gpu
+def test_gpu_hot_words_in_lds_or_hbm(gpu_native):
+    """The per-(unit, VC) words in LDS (the default when they fit), in HBM on
+    request, and in HBM because they do not fit (8x8 mesh, 8 VCs: 5 x 3072
+    words > 48 KB): the same results every time."""
+    text = _icnt(**MECH_KEYS)
+    ref = _reference(gpu_native, "mech", text, MECH_POINTS)
+    _same(_batch(gpu_native, text, MECH_POINTS, "gpu", lds=False), ref)
+    assert gpu_native.icnt_open_loop_batch_stats()["lds_chunks"] == 0
+    big = _icnt(k=8, n=2, topology="mesh", num_vcs=8, vc_buf_size=2)
+    points = [_pt(rate=0.4, flits=2, cycles=120, warmup=20), _pt("transpose", 0.8, 1, cycles=120, warmup=20)]
+    bref = _batch(gpu_native, big, points, "cpu")
+    assert all(r["packets"] > 0 for r in bref)
+    _same(_batch(gpu_native, big, points, "gpu"), bref)
+    assert gpu_native.icnt_open_loop_batch_stats()["lds_chunks"] == 0
+
+
+TOPOLOGIES = [dict(MESH), dict(TORUS), dict(k=8, n=1), dict(k=2, n=3), dict(k=2, n=2, c=4, topology="cmesh"),
+              dict(k=2, n=3, topology="fattree"), dict(k=4, n=2, c=1, topology="flatfly")]
+FUZZ_CONFIGS, FUZZ_POINTS = 10, 4
+
+
+def _fuzz_draws():
+    rnd = random.Random(20240611)
+    draws = []
+    for _ in range(FUZZ_CONFIGS):
+        keys = dict(rnd.choice(TOPOLOGIES))
+        keys.update(num_vcs=rnd.randint(1, 4), vc_buf_size=rnd.randint(1, 8),
+                    internal_speedup=rnd.choice(["1.0", "1.5", "2.0"]), credit_delay=rnd.randint(0, 3),
+                    alloc_iters=rnd.randint(1, 3), sw_allocator=rnd.choice(ALLOCATORS))
+        if keys.get("topology") == "mesh" and keys["num_vcs"] >= 2:
+            keys["routing_function"] = rnd.choice(["dest_tag", "min_adapt", "valiant"])
+        points = [_pt(rnd.choice(["uniform", "uniform", "bitcomp", "transpose", "shuffle", "neighbor", "tornado"]),
+                      round(rnd.uniform(0.05, 1.0), 3), rnd.randint(1, 5), seed=rnd.randint(1, 1000))
+                  for _ in range(FUZZ_POINTS)]
+        draws.append((keys, points))
+    return draws
+
+
+def _fuzz_reference(native):
+    """Per configuration the points the host path accepts and their results;
+    a point the host refuses (ValueError) is skipped."""
+    if "fuzz" not in _ref:
+        kept, skipped = [], 0
+        for keys, points in _fuzz_draws():
+            text = _icnt(**keys)
+            ok = []
+            for p in points:
+                try:
+                    native.icnt_open_loop_batch(text, [p], engine="cpu")
+                    ok.append(p)
+                except ValueError:
+                    skipped += 1
+            if ok:
+                kept.append((text, ok, _batch(native, text, ok, "cpu")))
+        _ref["fuzz"] = (kept, skipped)
+    return _ref["fuzz"]
+
+
+def _check_fuzz(native, engine):
+    kept, skipped = _fuzz_reference(native)
+    assert skipped * 4 <= FUZZ_CONFIGS * FUZZ_POINTS, f"{skipped} draws refused by the host path"
+    assert sum(r["packets"] for _, _, ref in kept for r in ref) > 0
+    for text, points, ref in kept:
+        _same(_batch(native, text, points, engine), ref)
+
+
+def test_cpu_par_fuzz(native):
+    _check_fuzz(native, "cpu-par")
+
+
+@pytest.mark.gpu
+def test_gpu_fuzz(gpu_native):
+    _check_fuzz(gpu_native, "gpu")
+
+
+# ---- interface ----
+
+def test_batch_equals_single_runs(native):
+    text = _icnt(**MECH_KEYS)
+    got = native.icnt_open_loop_batch(text, MECH_POINTS[:3], engine="cpu")
+    for p, g in zip(MECH_POINTS[:3], got):
+        assert g == native.icnt_open_loop(text, *p)
+        assert "arrivals" not in g and "state" not in g
+    assert native.icnt_open_loop_batch(text, MECH_POINTS[:3]) == got  # the default engine
+    with pytest.raises(ValueError, match="engine"):
+        native.icnt_open_loop_batch(text, MECH_POINTS[:1], engine="tpu")
+
+
+def test_gpu_engine_without_device_raises(native):
+    import torch  # bind torch's HIP runtime before the device is looked for
+    torch.cuda.is_available()
+    text = _icnt(**MECH_KEYS)
+    if native.gpu_available():
+        assert len(native.icnt_open_loop_batch(text, MECH_POINTS[:1], engine="gpu")) == 1
+    else:
+        with pytest.raises(RuntimeError, match="HIP device"):
+            native.icnt_open_loop_batch(text, MECH_POINTS[:1], engine="gpu")
+
+
+def test_step_cap_reports_status(native):
+    """The loop guard: a pass cut off by its step cap (here a test-only cap far
+    below the pass's size) ends with a status error that names the point."""
+    text = _icnt(**MECH_KEYS)
+    with pytest.raises(RuntimeError, match="point 0.*step cap"):
+        native.icnt_open_loop_batch(text, MECH_POINTS[:3], engine="cpu-par", step_cap=5)
+    # the sequential pass has no guard and ignores the option
+    assert len(native.icnt_open_loop_batch(text, MECH_POINTS[:3], engine="cpu", step_cap=5)) == 3
+
+
+def _cli(capsys, argv):
+    from accel_sim_framework_distributed_amd.icnt import booksim
+    assert booksim.main(argv) == 0
+    return capsys.readouterr().out
+
+
+def test_cli_engine_cpu_par_prints_the_same(tmp_path, capsys):
+    f = tmp_path / "x.icnt"
+    f.write_text(_icnt(**MECH_KEYS))
+    base = [str(f), "--rates", "0.2,0.8", "--cycles", str(CYC), "--warmup", str(WARM), "--packet-flits", "2"]
+    j0, j1 = tmp_path / "a.json", tmp_path / "b.json"
+    t0 = _cli(capsys, base + ["--json", str(j0)])
+    t1 = _cli(capsys, base + ["--json", str(j1), "--engine", "cpu-par"])
+    assert t0 == t1 and t0.count("Overall average latency") == 2
+    assert j0.read_bytes() == j1.read_bytes()
+    # the default output is what the single-run path gives
+    from accel_sim_framework_distributed_amd.icnt import booksim
+    curve = json.load(open(j0))["curve"]
+    for c, r in zip(curve, (0.2, 0.8)):
+        d = booksim.run(f.read_text(), r, packet_flits=2, cycles=CYC, warmup=WARM)
+        d["rate"] = r
+        assert c == d and list(c) == list(d)
+
+
+def test_cli_traffic_list_and_seeds(tmp_path, capsys):
+    f = tmp_path / "x.icnt"
+    f.write_text(_icnt(**MECH_KEYS))
+    j = tmp_path / "a.json"
+    text = _cli(capsys, [str(f), "--rates", "0.2,0.6", "--cycles", str(CYC), "--warmup", str(WARM), "--traffic",
+                         "uniform,transpose", "--seeds", "3", "--engine", "cpu-par", "--json", str(j)])
+    assert text.count("Overall average latency") == 4 and text.count("Saturation") == 2
+    assert text.count("Traffic transpose") == 2
+    curve = json.load(open(j))["curve"]
+    assert [(c["traffic"], c["rate"], c["seed"]) for c in curve] == \
+        [(t, r, s) for t in ("uniform", "transpose") for r in (0.2, 0.6) for s in (1, 2, 3)]
+
+
+@pytest.mark.gpu
+def test_cli_engine_gpu_json_matches_cpu(gpu_native, tmp_path, capsys):
+    f = tmp_path / "x.icnt"
+    f.write_text(_icnt(**MECH_KEYS))
+    base = [str(f), "--rates", "0.2,0.8", "--cycles", str(CYC), "--warmup", str(WARM), "--traffic",
+            "uniform,transpose", "--seeds", "4"]
+    j0, j1 = tmp_path / "a.json", tmp_path / "b.json"
+    t0 = _cli(capsys, base + ["--json", str(j0), "--engine", "cpu"])
+    t1 = _cli(capsys, base + ["--json", str(j1), "--engine", "gpu"])
+    assert t0 == t1
+    assert json.load(open(j0)) == json.load(open(j1)) and len(json.load(open(j0))["curve"]) == 16
