@@ -11,8 +11,9 @@ build is exercised in a fresh child with its environment set beforehand
 
 MANIFEST.json: [{"name", "kernelslist", "preset", "extra"}, ...].  One JSON line
 per application goes to stdout: cycles, instructions, per-kernel cycles, the
-statistics, the SHA-256 of the engine's state image, and the kernel variant
-and block count the engine reports for its last launch.  The run fails if
+statistics, the SHA-256 of the engine's state image, the kernel variant and
+block count the engine reports for its last launch, and the router pass's
+counters (-sim_router_pass).  The run fails if
 that variant is not VARIANT, so a mistyped variable cannot pass as a test of
 the default build.
 """
@@ -36,7 +37,8 @@ def run_app(app: dict) -> dict:
     return dict(name=app["name"], engine=r.engine, deadlock=r.deadlock, tot_cycle=r.tot_cycle, tot_insn=r.tot_insn,
                 kernel_cycles=[k["cycles"] for k in r.kernels], stats=r.stats,
                 snapshot_sha256=hashlib.sha256(bytes(s.native.snapshot())).hexdigest(),
-                variant=m.group(1) if m else None, blocks=int(m.group(2)) if m else 0, wall_s=round(wall, 3))
+                variant=m.group(1) if m else None, blocks=int(m.group(2)) if m else 0, wall_s=round(wall, 3),
+                router_pass=r.router_pass)
 
 
 def main(argv) -> int:

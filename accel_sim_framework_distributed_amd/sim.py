@@ -50,6 +50,9 @@ class SimResult:
     output: str
     engine: str
     deadlock: bool
+    # -sim_router_pass: mode, passes, max_packets_req / _rep, split_blocks
+    # (native Simulator.router_pass_stats)
+    router_pass: Dict = dataclasses.field(default_factory=dict)
 
     @property
     def kips(self) -> float:
@@ -76,7 +79,7 @@ class Simulator:
         if rc != 0 and not n.deadlock:
             raise RuntimeError("simulation failed:\n" + n.output[-2000:])
         return SimResult(n.tot_insn, n.tot_cycle, wall, n.sim_seconds, n.kernels, n.collectives, n.output,
-                         n.engine, n.deadlock)
+                         n.engine, n.deadlock, n.router_pass_stats())
 
 
 def simulate(trace: str, config: ConfigLike = "QV100", engine: str = "cpu",

@@ -114,6 +114,7 @@ py::dict cfg_dict(const SimCfg& c) {
   d["ldst_resp_buf"] = c.ldst_resp_buf;
   d["icnt_in_pkts"] = c.icnt_in_pkts;
   d["icnt_out_limit"] = c.icnt_out_limit;
+  d["router_pass"] = std::string(c.router_pass == 1 ? "par" : "serial");
   return d;
 }
 
@@ -705,6 +706,19 @@ PYBIND11_MODULE(_asim, m) {
                return f(d, now).cast<uint64_t>();
              });
            })
+      .def("router_pass_stats",
+           [](Simulator& s) {
+             const RouterPassStats r = s.engine().router_pass_stats();
+             py::dict d;
+             d["mode"] = std::string(r.mode);
+             d["passes"] = r.passes;
+             d["max_packets_req"] = r.max_packets_req;
+             d["max_packets_rep"] = r.max_packets_rep;
+             d["split_blocks"] = r.split_blocks;
+             return d;
+           },
+           "-sim_router_pass: the mode and, under par, the subnet passes run, their largest packet counts and "
+           "the blocks that share an epoch's pass")
       .def("snapshot",
            [](Simulator& s) {
              std::vector<uint8_t> v;

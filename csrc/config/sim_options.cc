@@ -360,6 +360,12 @@ const OptDef kOptions[] = {
      "(the release / acquire of a multi-XCD GPU, whose XCD L2s are not coherent with each other)"},
     {"-sim_cpu_threads", 'u', "1", "CPU engine: OpenMP threads over the units of one epoch (1 = serial; "
                                   "run simulations job-parallel instead)"},
+    {"-sim_router_pass", 's', "serial",
+     "-icnt_link_contention 2: serial | par, the epoch pass over the routers: one lane (rt_simulate) or the "
+     "lane-parallel pass (rt_simulate_par; on the GPU engine 64 lanes and one block per subnet); same results"},
+    {"-sim_router_step_cap", 'u', "0",
+     "-sim_router_pass par: loop iterations after which a pass gives up with an error (0 = the pass's own bound; "
+     "a diagnostic)"},
     {"-collective_slice_bytes", 'u', "131072", "packet model: bytes per link packet (RCCL slice)"},
     {"-collective_max_channels", 'u', "16", "packet model: max parallel rings (channels)"},
     {"-collective_reduce_gbps", 'f', "900.0", "packet model: local memory bandwidth for reduce/copy (GB/s)"},
@@ -977,6 +983,12 @@ SimCfg derive_sim_cfg(const OptionRegistry& r) {
     c.mall_miss_fs = (uint64_t)r.getu("-sim_mall_miss_latency");  // cycles; fs once the clocks are known
   }
   c.cpu_threads = r.getu("-sim_cpu_threads");
+  {
+    const std::string rp = strip_ws(r.gets("-sim_router_pass"));
+    if (rp != "serial" && rp != "par") throw OptionError("-sim_router_pass must be serial or par, not '" + rp + "'");
+    c.router_pass = rp == "par" ? 1u : 0u;
+    c.router_step_cap = r.getu("-sim_router_step_cap");
+  }
   c.trace_mask = 0;
   if (r.getb("-trace_enabled")) {
     static const std::pair<const char*, uint32_t> streams[] = {

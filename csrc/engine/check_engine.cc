@@ -86,6 +86,7 @@ class CheckEngine final : public Engine {
     b_->flush_l2(writeback);
   }
   void stats(std::vector<SMStats>& sm, std::vector<MemStats>& mem) override { a_->stats(sm, mem); }
+  RouterPassStats router_pass_stats() override { return a_->router_pass_stats(); }
   void snapshot(std::vector<uint8_t>& out) override { a_->snapshot(out); }
   void restore(const std::vector<uint8_t>& in) override {
     a_->restore(in);

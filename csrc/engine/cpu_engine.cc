@@ -12,6 +12,7 @@
 #include <exception>
 #include <mutex>
 
+#include "../model/icnt_router_par.h"
 #include "engine.h"
 #include "thread_team.h"
 #include "trace_window.h"
@@ -158,6 +159,7 @@ class CpuEngine : public Engine {
     link_free_.clear();
     link_refs_.clear();
     n_link_state_ = 0;
+    rt_pc_ = RtPassCount{};
     if (c.link_contention && (icnt_link_count(c) > kMaxIcntLinks || !icnt_contention_fits(c, cap_req_, cap_rep_) ||
                               icnt_scratch_words(c, cap_req_, cap_rep_) > kMaxIcntScratchWords))
       throw std::runtime_error("-icnt_link_contention: topology or mailboxes too large for the link pass");
@@ -291,8 +293,17 @@ class CpuEngine : public Engine {
           // their routes before any destination reads them (icnt_links.h)
           if (tid == 0) {
             try {
-              icnt_epoch_pass<SeqPar>(c, box_req_[cur].data(), cnt_req_[cur].data(), cap_req_, box_rep_[cur].data(),
-                                      cnt_rep_[cur].data(), cap_rep_, link_free_.data(), link_refs_.data());
+              if (router_par()) {
+                // -sim_router_pass par: the lane-parallel pass on the host's
+                // lane policy, both subnets in turn over the one scratch
+                if (rt_epoch_run_par<SeqPar>(c, box_req_[cur].data(), cnt_req_[cur].data(), cap_req_,
+                                             box_rep_[cur].data(), cnt_rep_[cur].data(), cap_rep_, link_free_.data(),
+                                             link_refs_.data(), RT_DIR_BOTH, &rt_pc_) != RT_STATUS_OK)
+                  throw std::runtime_error(kRouterStepCapMsg);
+              } else {
+                icnt_epoch_pass<SeqPar>(c, box_req_[cur].data(), cnt_req_[cur].data(), cap_req_, box_rep_[cur].data(),
+                                        cnt_rep_[cur].data(), cap_rep_, link_free_.data(), link_refs_.data());
+              }
             } catch (...) {
               fail();
             }
@@ -476,6 +487,17 @@ class CpuEngine : public Engine {
     *wait_cycles = n_link_state_ ? link_free_[n_link_state_ + 1] : 0;
     if (deadlocked) *deadlocked = n_link_state_ ? link_free_[n_link_state_ + 2] : 0;
   }
+  bool router_par() const { return c_.link_contention == 2 && c_.router_pass == 1 && !link_free_.empty(); }
+  RouterPassStats router_pass_stats() override {
+    RouterPassStats r;
+    r.mode = c_.router_pass == 1 ? "par" : "serial";
+    if (!router_par()) return r;
+    r.passes = rt_pc_.passes[0] + rt_pc_.passes[1];
+    r.max_packets_req = rt_pc_.max_np[0];
+    r.max_packets_rep = rt_pc_.max_np[1];
+    r.split_blocks = 1;
+    return r;
+  }
   void advance(uint64_t cycles) override {
     uint64_t E = c_.icnt_latency;
     cycle_ += (cycles + E - 1) / E * E;
@@ -585,6 +607,7 @@ class CpuEngine : public Engine {
   std::vector<uint64_t> link_free_;
   std::vector<uint32_t> link_refs_;
   size_t n_link_state_ = 0;
+  RtPassCount rt_pc_{};  // -sim_router_pass par (thread 0 writes it)
   uint64_t epoch_ = 0, cycle_ = 0;
   KernelTab kt_{};
 };

@@ -45,6 +45,15 @@ struct RunResult {
   bool cap = false;  // stopped by -gpgpu_max_insn / -gpgpu_max_cta / -gpgpu_max_completed_cta
 };
 
+struct RouterPassStats {
+  const char* mode = "serial";  // -sim_router_pass
+  uint64_t passes = 0;          // subnet passes that had packets
+  uint32_t max_packets_req = 0, max_packets_rep = 0;  // the largest packet count of one pass per subnet
+  uint32_t split_blocks = 0;    // blocks (host: threads) that share an epoch's pass: 1 or 2; 0 when it does not run
+};
+// the message both engines throw when the lane-parallel pass reports RT_STATUS_STEP_CAP
+constexpr const char* kRouterStepCapMsg = "router pass hit its step cap (-sim_router_step_cap / rt_step_cap)";
+
 class Engine {
  public:
   virtual ~Engine() = default;
@@ -106,6 +115,9 @@ class Engine {
     *wait_cycles = 0;
     if (deadlocked) *deadlocked = 0;
   }
+  // -sim_router_pass: how the router model's epoch pass ran (kept outside the
+  // state image; the counts are filled by the lane-parallel pass only)
+  virtual RouterPassStats router_pass_stats() { return RouterPassStats{}; }
   // in-loop power sampling (PwrArm); engines without it return false
   virtual bool power_sampler() const { return false; }
   virtual void power_arm(const PwrArm&) { throw std::runtime_error("engine has no in-loop power sampler"); }
@@ -208,8 +220,8 @@ void gpu_pool_trim();  // give the allocator's cached blocks back to the driver
 // work (engine/icnt_sweep.hip); std::runtime_error when the device has none
 void* gpu_pool_alloc(size_t bytes);
 void gpu_pool_release(void* p);
-std::map<std::string, uint64_t> gpu_batch_stats();
-std::map<std::string, std::map<std::string, uint64_t>> gpu_engine_modes();  // per engine build: LDS, blocks per CU, registers  // global-state batch launches: batches, launches, blocks per CU
+std::map<std::string, uint64_t> gpu_batch_stats();  // global-state batch launches: batches, launches, blocks per CU
+std::map<std::string, std::map<std::string, uint64_t>> gpu_engine_modes();  // per engine build: LDS, blocks per CU, registers
 // compiled resources of the persistent engine kernel (empty if no HIP build):
 // registers, scratch, static LDS, plus the dynamic LDS the engine requests
 struct EngineKernelInfo {

@@ -21,6 +21,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../model/icnt_router_par.h"
 #include "engine.h"
 #include "grid_barrier.h"
 #include "wave_par.h"
@@ -75,6 +76,10 @@ struct GpuArgs {
   L2Line* mall;  // [n_mem][mall_sets * mall_assoc] or nullptr
   uint64_t* link_free;  // -icnt_link_contention: [links] free times, then 2 statistics words; or nullptr
   uint32_t* link_refs;  // the pass's packet list
+  // -sim_router_pass par: block 1's own scratch for the reply subnet (nullptr:
+  // one block runs both subnets over link_refs) and the pass's host counters
+  uint32_t* link_refs2;
+  RtPassCount* rt_pc;
   uint64_t epoch0;
   uint64_t cycle0;
   uint64_t max_cycle;
@@ -438,10 +443,27 @@ __device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) 
       // shared links of multi-hop routes: block 0 walks this epoch's packets
       // in the fixed order (icnt_links.h), then every block waits for it
       // before a destination reads them
-      if (b == 0)
+      // -sim_router_pass par (router model): all lanes of block 0 run the
+      // request subnet while block 1 runs the reply subnet over a scratch of
+      // its own (block 0 both when the simulation has one block); the subnets
+      // share only the statistics words (P::add64)
+      const bool rt_par = c.link_contention == 2 && c.router_pass == 1;
+      if (rt_par) {
+        if (b < 2) {
+          const uint32_t dirs = !a.link_refs2 ? (uint32_t)RT_DIR_BOTH : b == 0 ? (uint32_t)RT_DIR_REQ : (uint32_t)RT_DIR_REP;
+          const uint32_t rs = rt_epoch_run_par<P>(c, a.box_req[cur], a.cnt_req[cur], a.cap_req, a.box_rep[cur],
+                                                  a.cnt_rep[cur], a.cap_rep, a.link_free,
+                                                  b == 0 ? a.link_refs : a.link_refs2, dirs, a.rt_pc);
+          // a pass that gave up: every block leaves at the barrier below
+          if (rs != RT_STATUS_OK && (threadIdx.x & 63) == 0)
+            __hip_atomic_store(&a.ctl->error, kCtlErrRouterCap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else if (b == 0) {
         icnt_epoch_pass<P>(c, a.box_req[cur], a.cnt_req[cur], a.cap_req, a.box_rep[cur], a.cnt_rep[cur], a.cap_rep,
                            a.link_free, a.link_refs);
+      }
       if (!grid_barrier_b(a.ctl, b, a.nblocks, nbar++)) break;
+      if (rt_par && P::uni(__hip_atomic_load(&a.ctl->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
     }
     P::prof(27);  // decision
     if (a.ework) {

@@ -750,6 +750,13 @@ class GpuEngine : public Engine {
       pool_alloc(&d_links_, sizeof(uint64_t) * (n_links_ + kIcntStatWords));
       HIPCHECK(hipMemset(d_links_, 0, sizeof(uint64_t) * (n_links_ + kIcntStatWords)));
       pool_alloc(&d_link_refs_, sizeof(uint32_t) * (size_t)icnt_scratch_words(c, cap_req_, cap_rep_));
+      if (router_par()) {
+        // -sim_router_pass par: block 1 runs the reply subnet over a scratch
+        // of its own; the pass's counters for the host
+        if (nblocks_ >= 2) pool_alloc(&d_link_refs2_, sizeof(uint32_t) * (size_t)icnt_scratch_words(c, cap_req_, cap_rep_));
+        pool_alloc(&d_rt_pc_, sizeof(RtPassCount));
+        HIPCHECK(hipMemset(d_rt_pc_, 0, sizeof(RtPassCount)));
+      }
     }
     pool_alloc(&d_ctl_, sizeof(GpuCtl));
     h_ctl_ = static_cast<GpuCtl*>(DevicePool::get().host(sizeof(GpuCtl)));
@@ -811,6 +818,8 @@ class GpuEngine : public Engine {
       a.mall = d_mall_;
       a.link_free = d_links_;
       a.link_refs = d_link_refs_;
+      a.link_refs2 = d_link_refs2_;
+      a.rt_pc = d_rt_pc_;
       a.epoch0 = epoch_;
       a.cycle0 = cycle_;
       a.max_cycle = lim.max_cycle;
@@ -879,6 +888,7 @@ class GpuEngine : public Engine {
       HIPCHECK(ce);
       HIPCHECK(se);
       }
+      if (h_ctl_->error == kCtlErrRouterCap) throw std::runtime_error(kRouterStepCapMsg);
       if (h_ctl_->error) throw std::runtime_error("GPU engine: grid barrier timed out (blocks not co-resident?)");
       epoch_ = h_ctl_->end_epoch;
       cycle_ = h_ctl_->end_cycle;
@@ -971,6 +981,19 @@ class GpuEngine : public Engine {
     *delayed = st[0];
     *wait_cycles = st[1];
     if (deadlocked) *deadlocked = st[2];
+  }
+  bool router_par() const { return c_.link_contention == 2 && c_.router_pass == 1 && icnt_contention_on(c_); }
+  RouterPassStats router_pass_stats() override {
+    RouterPassStats r;
+    r.mode = c_.router_pass == 1 ? "par" : "serial";
+    if (!d_rt_pc_) return r;
+    RtPassCount pc{};
+    HIPCHECK(hipMemcpy(&pc, d_rt_pc_, sizeof(pc), hipMemcpyDeviceToHost));
+    r.passes = pc.passes[0] + pc.passes[1];
+    r.max_packets_req = pc.max_np[0];
+    r.max_packets_rep = pc.max_np[1];
+    r.split_blocks = d_link_refs2_ ? 2 : 1;
+    return r;
   }
   void advance(uint64_t cycles) override {
     uint64_t E = c_.icnt_latency;
@@ -1176,6 +1199,10 @@ class GpuEngine : public Engine {
     fr(d_mall_);
     fr(d_links_);
     fr(d_link_refs_);
+    fr(d_link_refs2_);
+    fr(d_rt_pc_);
+    d_link_refs2_ = nullptr;
+    d_rt_pc_ = nullptr;
     n_links_ = 0;
     fr(d_trace_ev_);
     fr(d_trace_cnt_);
@@ -1207,6 +1234,8 @@ class GpuEngine : public Engine {
   size_t n_mall_ = 0;
   uint64_t* d_links_ = nullptr;     // -icnt_link_contention: link free times + 2 statistics words
   uint32_t* d_link_refs_ = nullptr;
+  uint32_t* d_link_refs2_ = nullptr;  // -sim_router_pass par: block 1's scratch
+  RtPassCount* d_rt_pc_ = nullptr;    // and the pass's counters (read by router_pass_stats)
   size_t n_links_ = 0;
   uint32_t ovf_cap_ = 0;
   Pkt* d_box_req_[2] = {nullptr, nullptr};

@@ -13,7 +13,7 @@ struct GpuCtl {  // zeroed by hipMemsetAsync before every launch
   uint32_t arrive[8][64];     // per-group arrival counters (one 256-B line each)
   uint32_t gen[8][64];        // per-group generation words: each group polls its own line
   uint32_t top[64];           // group leaders' counter
-  uint32_t error;             // barrier timeout / fault code
+  uint32_t error;             // barrier timeout / fault code (kCtlErr*)
   uint32_t done;
   uint32_t deadlock;
   uint32_t cap;  // a run cap (-gpgpu_max_insn / _max_cta / _max_completed_cta) ended the launch
@@ -21,6 +21,11 @@ struct GpuCtl {  // zeroed by hipMemsetAsync before every launch
   uint64_t end_epoch;
   uint64_t epochs_run;
 };
+
+// GpuCtl::error: a block that stores one goes on to the next barrier, where
+// every block leaves the launch
+constexpr uint32_t kCtlErrBarrier = 1;    // a grid barrier timed out
+constexpr uint32_t kCtlErrRouterCap = 2;  // the lane-parallel router pass hit its step cap
 
 // grid barrier: blocks are grouped by blockIdx % 8 (which shares an XCD under
 // the observed round-robin placement: a speed hint only, correctness does not

@@ -307,6 +307,12 @@ struct WavePar {
   static __device__ __forceinline__ void min32(uint32_t* p, uint32_t v) {
     (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
+  // order-free sum into one word from several waves (hd.h SeqPar::add64):
+  // lane 0's agent-scope atomic add (a vector memory atomic, relaxed); the
+  // grid barrier's release / acquire publishes it
+  static __device__ __forceinline__ void add64(uint64_t* p, uint64_t v) {
+    if (lane() == 0) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   // exclusive scan: within-row Hillis-Steele on row_shr:1/2/4/8 (lanes
   // shifted in from outside the row read 0), then the row totals via readlane
   template <class F, class G>

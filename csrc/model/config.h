@@ -369,6 +369,11 @@ struct SimCfg {
   uint32_t mall_sets, mall_assoc;
   uint64_t mall_miss_fs;    // extra latency of a MALL miss (fs)
   uint32_t cpu_threads;     // CPU engine only: OpenMP threads per epoch (host option)
+  // -sim_router_pass (engine option, like cpu_threads; no effect on results):
+  // the epoch pass of -icnt_link_contention 2 is the serial rt_simulate (0)
+  // or the lane-parallel rt_simulate_par (1, icnt_router_par.h)
+  uint32_t router_pass;
+  uint64_t router_step_cap;  // -sim_router_step_cap: loop guard of the lane-parallel pass (0: rt_step_cap)
   // ---- debug trace streams (pointers are set by the engine that owns the buffers) ----
   uint32_t trace_mask;      // TraceStream bits
   int32_t trace_sm;         // -trace_sampling_core (-1: all)

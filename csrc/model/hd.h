@@ -186,6 +186,10 @@ struct SeqPar {
   static SIM_HDI void min32(uint32_t* p, uint32_t v) {
     if (v < *p) *p = v;
   }
+  // *p += v once per wave, from wave-uniform code (v uniform), on a word that
+  // another wave may add to in the same phase: a sum does not depend on the
+  // order.  Readers come after the next grid barrier.
+  static SIM_HDI void add64(uint64_t* p, uint64_t v) { *p += v; }
   // the members of `mask` (indices < n <= 16) sorted by key ascending (ties
   // to the lower index), packed 4 bits per entry: entry r = (ord >> 4r) & 15.
   // Replaces repeated "oldest remaining" argmin scans with one ranking.

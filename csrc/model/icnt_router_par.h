@@ -55,6 +55,10 @@
 // cut off after kRtGuardFactor * E + U + 64 iterations (a factor 2 would do
 // for a correct pass; 4 leaves a margin) and the pass reports
 // RT_STATUS_STEP_CAP: a bug ends the pass instead of spinning it.
+//
+// Users: the open-loop sweep kernel (engine/icnt_sweep.hip, one wavefront per
+// network) and, under -sim_router_pass par, the cycle engines' epoch pass
+// (rt_epoch_run_par at the end of this file).
 #pragma once
 #include "icnt_router.h"
 
@@ -738,6 +742,105 @@ SIM_HDI uint32_t rt_simulate_par(const SimCfg& c, const RtDims& d, uint64_t* st,
                                  uint64_t* act = nullptr, uint32_t* status = nullptr, uint64_t step_cap = 0) {
   const RtHot<uint32_t*> hv{w.vhead, w.vcnt, w.vown, w.vout, w.vocc};
   return rt_simulate_par_hot<P>(c, d, st, w, hv, np, act, status, step_cap);
+}
+
+// ---- the cycle engines' epoch pass (-sim_router_pass par) ----
+// rt_epoch_run (icnt_router.h) against the lane policy, one subnet or both:
+// the same packets in the same order through rt_simulate_par, so the delays,
+// the subnets' state words and the statistics are those of rt_epoch_run.
+enum RtDir : uint32_t { RT_DIR_REQ = 1, RT_DIR_REP = 2, RT_DIR_BOTH = 3 };
+
+// counters of the lane-parallel epoch pass for the host (outside the state
+// image), per direction so that two blocks never write one word
+struct RtPassCount {
+  uint64_t passes[2];  // subnet passes that had packets {request, reply}
+  uint32_t max_np[2];  // the largest packet count of one
+};
+
+// `dirs`: RtDir bits; `scratch`: rt_carve(rt_epoch_dims) words of this
+// caller's own (two callers running one direction each share only `st`'s
+// statistics words, which take P::add64).  Returns RT_STATUS_*: after
+// RT_STATUS_STEP_CAP the pass's delays are not applied and the run must end.
+template <class P>
+SIM_HDN uint32_t rt_epoch_run_par(const SimCfg& c, Pkt* box_req, const uint32_t* cnt_req, uint32_t cap_req,
+                                  Pkt* box_rep, const uint32_t* cnt_rep, uint32_t cap_rep, uint64_t* st,
+                                  uint32_t* scratch, uint32_t dirs, RtPassCount* pc) {
+  const RtDims d = rt_epoch_dims(c, cap_req, cap_rep);
+  RtWork w;
+  rt_carve(d, scratch, &w);
+  uint64_t* stat = st + 2 * rt_state_words(d);
+  const uint32_t ncell = c.n_sm * c.n_subpart;
+  const uint32_t cpc = c.cores_per_cluster ? c.cores_per_cluster : 1;
+  const uint32_t nfl_max = rt_flits(c, kRtMaxPktBytes);  // the scratch holds nfl_max flits per packet
+  for (uint32_t dir = 0; dir < 2; ++dir) {
+    if (!(dirs >> dir & 1u)) continue;
+    const uint32_t* cnt = dir == 0 ? cnt_req : cnt_rep;
+    Pkt* box = dir == 0 ? box_req : box_rep;
+    const uint32_t cap = dir == 0 ? cap_req : cap_rep;
+    // gather: the packets by cell, then by slot; a cell's first packet index
+    // by an ordered scan over the cells' counts (staged in w.roff, which the
+    // pass's setup rewrites; ncell <= d.np)
+    auto cell_n = [&](int cell) -> uint32_t { return cnt[cell] < cap ? cnt[cell] : cap; };
+    const uint32_t np = P::scan((int)ncell, cell_n, [&](int cell, uint32_t x) { w.roff[cell] = x; });
+    if (!np) continue;
+    P::sync();
+    P::each((int)ncell, [&](int ci) {
+      const uint32_t cell = (uint32_t)ci, n = cell_n(ci);
+      if (!n) return;
+      uint32_t a, b, sm, sub;
+      if (dir == 0) {  // request: SM (cell % n_sm) -> sub-partition (cell / n_sm)
+        sm = cell % c.n_sm;
+        sub = cell / c.n_sm;
+        a = sm / cpc;
+        b = c.n_clusters + sub;
+      } else {  // reply: sub-partition (cell % n_subpart) -> SM (cell / n_subpart)
+        sub = cell % c.n_subpart;
+        sm = cell / c.n_subpart;
+        a = c.n_clusters + sub;
+        b = sm / cpc;
+      }
+      const uint64_t lat = icnt_pkt_lat_fs(c, sm, sub);
+      const uint32_t o = w.roff[cell];
+      for (uint32_t j = 0; j < n; ++j) {
+        const Pkt& p = box[(uint64_t)cell * cap + j];
+        const uint64_t t0 = p.t > lat ? p.t - lat : 0;
+        const uint32_t nfl = rt_flits(c, p.size ? p.size : 1);
+        w.src[o + j] = a;
+        w.dst[o + j] = b;
+        w.nfl[o + j] = nfl < nfl_max ? nfl : nfl_max;
+        w.tinj[o + j] = fdiv(t0, c.dv_icnt);
+        w.bidx[o + j] = cell * cap + j;
+      }
+    });
+    P::sync();
+    // the pass; its status comes back through a scratch word every lane can read
+    uint32_t* stw = w.ge;
+    const uint32_t lost =
+        rt_simulate_par<P>(c, d, st + (uint64_t)dir * rt_state_words(d), w, np, nullptr, stw, c.router_step_cap);
+    if (P::uni(*stw) != RT_STATUS_OK) return RT_STATUS_STEP_CAP;
+    // write-back: a packet's delay into its own mailbox slot
+    uint64_t delayed = 0, wait = 0;
+    P::lane_loop((int)np, [&](int i) {
+      const uint64_t base = w.tinj[i] + rt_uncontended(c, icnt_routers(c, w.src[i], w.dst[i]), w.nfl[i]);
+      const uint64_t D = w.tarr[i] > base ? w.tarr[i] - base : 0;
+      if (D) {
+        ++delayed;
+        wait += D;
+        box[w.bidx[i]].t += D * c.per_icnt;
+      }
+    });
+    delayed = P::red_sum64(delayed);
+    wait = P::red_sum64(wait);
+    if (delayed) P::add64(&stat[0], delayed);
+    if (wait) P::add64(&stat[1], wait);
+    if (lost) P::add64(&stat[2], lost);  // routing deadlock: those packets kept their uncontended latency
+    if (pc) P::one([&] {
+      ++pc->passes[dir];
+      if (np > pc->max_np[dir]) pc->max_np[dir] = np;
+    });
+    P::sync();
+  }
+  return RT_STATUS_OK;
 }
 
 }  // namespace asim
