@@ -41,8 +41,22 @@
 // Booksim's standalone mode): there every packet is known up front and the
 // simulation is exact cycle by cycle.
 //
-// Sequential and policy-generic (P::one): the CPU and GPU engines produce
-// identical results.
+// Two drivers run the pass and give bit for bit the same results on every
+// engine.  What they share is defined once, in RtCtx below: the constants
+// derived from the configuration, a packet's route and flit table, the source
+// queues' linking, the VC rules (free_vc, adapt_choice), whether a head flit
+// may ask for the switch, the four order-sensitive allocators, the commit and
+// switch traversal of a matched pair, the event times and a deadlocked
+// packet's arrival; for the epoch pass also the mailbox cell's nodes, a
+// packet's fields and its delay (rt_cell, rt_fill_packet, rt_packet_delay).
+// What a driver owns is the control flow: the main loop, the credit FIFO
+// walk, the injection loop, the request list's packing, the separable and
+// iSLIP matching, the commit order, the retire step and the activity counts.
+//  * rt_simulate / rt_epoch_run (this file): one thread, plain loops over the
+//    lists; the default of the cycle engines (one lane under P::one on the
+//    device) and engine `cpu` of the open-loop mode;
+//  * rt_simulate_par / rt_epoch_run_par (icnt_router_par.h): the same phases
+//    against the lane policy, lists built by ordered scans.
 #pragma once
 #include "icnt_links.h"
 
@@ -225,11 +239,6 @@ SIM_HDI uint64_t rt_uncontended(const SimCfg& c, uint32_t routers, uint32_t nfl)
   return (uint64_t)routers * c.hop_icnt + (uint64_t)(routers + 1) * c.chan_icnt + (nfl - 1);
 }
 
-// Simulate the `np` packets already in w (src, dst, nfl, tinj) through one
-// subnet whose persistent state is `st` (rt_state_words); fills w.tarr (the
-// tail flit's arrival, icnt cycles) and returns the number of packets that
-// could not be delivered (a routing deadlock: they get their uncontended
-// traversal after the last delivery).  Single-threaded.
 // Router activity of a pass (the inputs of Booksim's power module,
 // intersim2/power/power_module.cpp): act[RT_ACT_*] when `act` is given.
 enum RtAct : int {
@@ -243,36 +252,83 @@ enum RtAct : int {
   RT_ACT_COUNT
 };
 
-SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, uint32_t np,
-                             uint64_t* act = nullptr) {
-  uint64_t* link_next = st;
-  uint64_t* gptr = st + d.L;
-  uint64_t* in_free = st + 2 * d.L;
-  uint64_t* aptr = st + 2 * d.L + d.U;
-  uint64_t* inj_next = st + 2 * d.L + 2 * d.U;
-  const uint32_t V = d.V, B = d.B, N = d.N, L = d.L, U = d.U;
-  const uint64_t head_delay = c.hop_icnt > 0 ? c.hop_icnt - 1u : 0u, body_delay = c.rt_sa, chan = c.chan_icnt;
-  const uint64_t slack = c.rt_speedup_q8 > 256 ? kRtOutSlack : 0;
-  const uint32_t iters = c.rt_iters ? c.rt_iters : 1;
-  const bool dateline = c.topo == TOPO_TORUS && V >= 2;
-  const uint32_t tk = c.topo_k ? c.topo_k : 2, tn = c.topo_n ? c.topo_n : 1;
+// The per-(unit, VC) words of a pass -- head, count, owner, output VC and
+// downstream occupancy of every input VC, the words every phase touches --
+// behind pointers of their own type: the work arrays' (RtWork, HBM on the
+// device) or, in the sweep kernel, LDS-typed pointers (U * V words each).
+template <class Ptr>
+struct RtHot {
+  Ptr vhead, vcnt, vown, vout, vocc;
+};
+
+// What a switch traversal did with flit f (RtHop).  `to` is one of
+//   an index below kRtDelivered  the downstream (unit, VC) the flit moved to;
+//                                the driver pushes it into that buffer
+//   kRtEject                     the flit left the network, its packet's tail
+//                                is still to come
+//   kRtDelivered                 the flit left the network as the tail: the
+//                                packet has arrived (w.tarr is set)
+constexpr uint32_t kRtEject = 0xfffffffeu;
+constexpr uint32_t kRtDelivered = 0xfffffffdu;
+struct RtHop {
+  uint32_t f, to;
+};
+
+// ---- the model both passes share ----
+// One pass's network: configuration, dimensions, scratch, the hot words, the
+// subnet's persistent state `st` (rt_state_words) and the constants derived
+// from the configuration.  The members are the router model proper -- what a
+// packet's route is, which VC a flit may take, when a head flit may ask for
+// the switch, whom an order-sensitive allocator matches, what a traversal
+// does, when something can move next.  They take one element (a packet, a
+// source, an input unit, a matched pair) and neither loop nor count: the
+// drivers (rt_simulate below, rt_simulate_par_hot in icnt_router_par.h)
+// decide the order and the parallelism and count the activity.
+template <class HV>
+struct RtCtx {
+  const SimCfg& c;
+  const RtDims& d;
+  const RtWork& w;
+  const HV hv;
+  uint64_t *const link_next, *const gptr, *const in_free, *const aptr, *const inj_next;
+  const uint32_t V, B, N, L, U;
+  const uint64_t head_delay, body_delay, chan, slack;
+  const uint32_t iters, alloc;
+  const uint32_t tk, tn;
+  const bool dateline;
   // minimal adaptive routing on meshes: VC 0 is the dimension-order escape
   // channel, VCs 1.. are adaptive (Duato); needs >= 2 VCs
-  const bool adaptive = c.rt_route == 1 && (c.topo == TOPO_MESH || c.topo == TOPO_CMESH) && V >= 2;
-  const uint32_t aconc = c.topo == TOPO_CMESH ? (c.topo_conc ? c.topo_conc : 1) : 1, aP = 2 * tn + aconc;
+  const bool adaptive;
+  const uint32_t aconc, aP;
   // Valiant (mesh): dimension order to a random intermediate router, then
   // dimension order to the destination; the second leg on the upper half of
   // the VCs (two classes keep the two legs' channel dependences acyclic)
-  const bool valiant = c.rt_route == 2 && (c.topo == TOPO_MESH || c.topo == TOPO_CMESH) && V >= 2;
-  // ---- routes, flits, source queues (injection order: time, then packet) ----
-  for (uint32_t s = 0; s < N; ++s) {
-    w.shead[s] = w.stail[s] = kRtNone;
-    w.sfl[s] = 0;
-    w.svc[s] = kRtNone;
-    w.sflag[s] = 0;
+  const bool valiant;
+
+  SIM_HDI RtCtx(const SimCfg& c_, const RtDims& d_, uint64_t* st, const RtWork& w_, const HV& hv_)
+      : c(c_), d(d_), w(w_), hv(hv_),
+        link_next(st), gptr(st + d_.L), in_free(st + 2 * d_.L), aptr(st + 2 * d_.L + d_.U),
+        inj_next(st + 2 * d_.L + 2 * d_.U),
+        V(d_.V), B(d_.B), N(d_.N), L(d_.L), U(d_.U),
+        head_delay(c_.hop_icnt > 0 ? c_.hop_icnt - 1u : 0u), body_delay(c_.rt_sa), chan(c_.chan_icnt),
+        slack(c_.rt_speedup_q8 > 256 ? kRtOutSlack : 0),
+        iters(c_.rt_iters ? c_.rt_iters : 1), alloc(c_.rt_alloc),
+        tk(c_.topo_k ? c_.topo_k : 2), tn(c_.topo_n ? c_.topo_n : 1),
+        dateline(c_.topo == TOPO_TORUS && d_.V >= 2),
+        adaptive(c_.rt_route == 1 && (c_.topo == TOPO_MESH || c_.topo == TOPO_CMESH) && d_.V >= 2),
+        aconc(c_.topo == TOPO_CMESH ? (c_.topo_conc ? c_.topo_conc : 1) : 1), aP(2 * tn + aconc),
+        valiant(c_.rt_route == 2 && (c_.topo == TOPO_MESH || c_.topo == TOPO_CMESH) && d_.V >= 2) {}
+
+  // wavefront, maximum size, PIM and LOA depend on the order of the request
+  // list (allocate_ordered); iSLIP and the two separable ones do not
+  SIM_HDI bool ordered_alloc() const {
+    return alloc == RT_WAVEFRONT || alloc == RT_MAX_SIZE || alloc == RT_PIM || alloc == RT_LOA;
   }
-  uint32_t nf = 0, nsrc = 0;
-  for (uint32_t p = 0; p < np; ++p) {
+  SIM_HDI bool one_shot_alloc() const { return alloc == RT_WAVEFRONT || alloc == RT_MAX_SIZE; }
+
+  // ---- setup ----
+  // Route and flit table of packet p, whose first flit is fb = w.fbase[p]
+  SIM_HDI void init_packet(uint32_t p, uint32_t fb) const {
     w.roff[p] = p * d.H;
     uint32_t h = 0, dim = ~0u, crossed = 0;
     if (adaptive) {
@@ -287,13 +343,10 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       const uint32_t nr = (uint32_t)ipow(tk, tn);
       const uint32_t mid = (uint32_t)(rt_hash(w.tinj[p] * 1000003u + w.src[p], w.dst[p]) % nr);
       const uint32_t mid_node = mid * aconc;
-      uint32_t leg1 = 0;
       icnt_route(c, w.src[p], mid_node, [&](uint32_t l) {
-        leg1 = l;  // (the last link is mid's ejection: dropped below)
         if (h < d.H) w.route[p * d.H + h] = l;
         ++h;
       });
-      (void)leg1;
       --h;  // drop the ejection link into the intermediate node
       icnt_route(c, mid_node, w.dst[p], [&](uint32_t l) {
         if (h < d.H) w.route[p * d.H + h] = l | 1u << 31;
@@ -327,15 +380,19 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       ++h;
     });
     w.nh[p] = h < d.H ? h : d.H;
-    w.fbase[p] = nf;
     for (uint32_t i = 0; i < w.nfl[p]; ++i) {
-      w.fpk[nf + i] = p;
-      w.fhop[nf + i] = 0;
+      w.fpk[fb + i] = p;
+      w.fhop[fb + i] = 0;
     }
-    nf += w.nfl[p];
     w.tarr[p] = 0;
-    const uint32_t s = w.src[p];
     w.next[p] = kRtNone;
+  }
+
+  // Link packet p (after init_packet, packets in index order) into its
+  // source's queue, kept in (injection time, packet) order; a source's first
+  // packet appends the source to the source list
+  SIM_HDI void link_source(uint32_t p, uint32_t& nsrc) const {
+    const uint32_t s = w.src[p];
     if (w.shead[s] == kRtNone) {
       w.shead[s] = w.stail[s] = p;
       w.sflag[s] = 1;
@@ -353,9 +410,339 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       w.next[q] = p;
     }
   }
+
+  // ---- input VC buffers ----
+  SIM_HDI uint32_t front(uint32_t uv) const { return w.ring[(uint64_t)uv * B + hv.vhead[uv]]; }
+  SIM_HDI void push(uint32_t uv, uint32_t f) const {
+    w.ring[(uint64_t)uv * B + (hv.vhead[uv] + hv.vcnt[uv]) % B] = f;
+    ++hv.vcnt[uv];
+  }
+  // a free VC with room on downstream unit du (kRtNone if none)
+  // VC class: dateline (torus) 0 lower / 1 upper half; adaptive 0 escape VC
+  // / 1 adaptive VCs; 2 any
+  SIM_HDI uint32_t free_vc(uint32_t du, uint32_t cls) const {
+    uint32_t v0 = 0, v1 = V;
+    if (cls < 2 && (dateline || valiant)) {
+      v0 = cls ? V / 2 : 0;
+      v1 = cls ? V : V / 2;
+    } else if (cls < 2 && adaptive) {
+      v0 = cls ? 1 : 0;
+      v1 = cls ? V : 1;
+    }
+    for (uint32_t v = v0; v < v1; ++v) {
+      const uint32_t i = du * V + v;
+      if (hv.vown[i] == kRtNone && hv.vocc[i] < B) return v;
+    }
+    return kRtNone;
+  }
+  // the head of packet p chooses its next link: the productive direction
+  // whose downstream unit has an adaptive VC with the most free slots
+  // (lowest dimension on ties), else the dimension-order link if its escape
+  // VC is free; kRtUnrouted if blocked.  Returns link | class << 31.
+  SIM_HDI uint32_t adapt_choice(uint32_t p) const {
+    const uint32_t cur = w.pcur[p], dst = w.dst[p] / aconc;
+    if (cur == dst) return cur * aP + 2 * tn + w.dst[p] % aconc;  // ejection
+    uint32_t best = kRtUnrouted, best_free = 0, esc = kRtUnrouted;
+    uint64_t pw = 1;
+    for (uint32_t dd = 0; dd < tn; ++dd, pw *= tk) {
+      const uint32_t x = (uint32_t)((cur / pw) % tk), y = (uint32_t)((dst / pw) % tk);
+      if (x == y) continue;
+      const uint32_t l = cur * aP + 2 * dd + (y > x ? 0u : 1u), du = N + l;
+      if (esc == kRtUnrouted) esc = l;
+      for (uint32_t v = 1; v < V; ++v) {
+        const uint32_t i = du * V + v;
+        if (hv.vown[i] == kRtNone && hv.vocc[i] < B && B - hv.vocc[i] > best_free) {
+          best_free = B - hv.vocc[i];
+          best = l;
+        }
+      }
+    }
+    if (best != kRtUnrouted) return best | 1u << 31;
+    if (esc != kRtUnrouted && free_vc(N + esc, 0) != kRtNone) return esc;
+    return kRtUnrouted;
+  }
+
+  // ---- switch requests ----
+  // The link the head flit of input VC (u, v) asks the switch for at `now`,
+  // kRtNone if it may not ask: no flit, not through its pipeline stages yet,
+  // an adaptive head with every choice blocked, no VC (head) or credit (body)
+  // downstream, or the output buffer ahead of its link by more than `slack`.
+  // An adaptive head's choice is written into its route; it reads only
+  // downstream state that no request changes.  `f`: that head flit (set when
+  // the VC holds one).
+  SIM_HDI uint32_t request(uint32_t u, uint32_t v, uint64_t now, uint32_t& f) const {
+    const uint32_t uv = u * V + v;
+    if (!hv.vcnt[uv]) return kRtNone;
+    f = front(uv);
+    if (w.ready[f] > now) return kRtNone;
+    const uint32_t p = w.fpk[f], h = w.fhop[f];
+    if (adaptive && f == w.fbase[p]) {
+      const uint32_t ch = adapt_choice(p);
+      if (ch == kRtUnrouted) return kRtNone;
+      w.route[w.roff[p] + h] = ch;
+    }
+    const uint32_t rl = w.route[w.roff[p] + h], l = rl & 0x7fffffffu;
+    const bool last = h + 1 >= w.nh[p];
+    if (!last) {
+      const uint32_t du = N + l;
+      if (f == w.fbase[p]) {
+        if (free_vc(du, rl >> 31) == kRtNone) return kRtNone;
+      } else if (hv.vocc[du * V + hv.vout[uv]] >= B) {
+        return kRtNone;
+      }
+    }
+    const uint64_t dep = link_next[l] > now + 1 ? link_next[l] : now + 1;
+    if (dep > now + 1 + slack) return kRtNone;
+    return l;
+  }
+  // of two VCs of an input unit that ask for the same link, the one whose
+  // head flit has been eligible longer asks: whether head flit f displaces
+  // the head flit of VC (u, v), which asked first
+  SIM_HDI bool older(uint32_t f, uint32_t u, uint32_t v) const { return w.ready[f] < w.ready[front(u * V + v)]; }
+
+  // ---- the order-sensitive allocators ----
+  // One iteration `it` over the request list rq_u / rq_v / rq_l[0 .. nrq)
+  // (an input unit's requests are contiguous), single-threaded: leaves the
+  // inputs' choice in a_tag / a_l / a_v and the outputs' in g_tag / g_in,
+  // stamped `tag`; pairs matched earlier in this switch pass carry `rtag` in
+  // m_u / m_l.  `dfs` stamps the maximum-size allocator's searches.
+  SIM_HDI void allocate_ordered(uint32_t nrq, uint64_t now, uint32_t tag, uint32_t rtag, uint32_t it,
+                                uint32_t& dfs) const {
+    if (alloc == RT_WAVEFRONT) {
+      // diagonal (u + l) mod n of the request matrix, from the priority
+      // diagonal of this cycle; within a diagonal no two cells share a
+      // row or a column
+      const uint32_t n = U > L ? U : L, pd = (uint32_t)(now % n);
+      for (uint32_t j = 0; j < nrq; ++j) {
+        w.rq_k[j] = (w.rq_u[j] + w.rq_l[j] + n - pd) % n;
+        uint32_t q = j;  // insertion into the order by (diagonal, request)
+        while (q > 0 && w.rq_k[w.rq_o[q - 1]] > w.rq_k[j]) {
+          w.rq_o[q] = w.rq_o[q - 1];
+          --q;
+        }
+        w.rq_o[q] = j;
+      }
+      for (uint32_t q = 0; q < nrq; ++q) {
+        const uint32_t j = w.rq_o[q], u = w.rq_u[j], l = w.rq_l[j];
+        if (w.a_tag[u] == tag || w.g_tag[l] == tag) continue;
+        w.a_tag[u] = w.g_tag[l] = tag;
+        w.a_l[u] = l;
+        w.a_v[u] = w.rq_v[j];
+        w.g_in[l] = u;
+      }
+    } else if (alloc == RT_MAX_SIZE) {
+      // maximum matching: an augmenting path from every input in turn
+      // (its requests are contiguous in the request list)
+      for (uint32_t j = 0; j < nrq; ++j) {
+        if (j == 0 || w.rq_u[j - 1] != w.rq_u[j]) w.gb[w.rq_u[j]] = j;
+        w.ge[w.rq_u[j]] = j + 1;
+      }
+      for (uint32_t j = 0; j < nrq; j = w.ge[w.rq_u[j]]) {
+        ++dfs;
+        uint32_t sp = 1;
+        w.st_u[0] = w.rq_u[j];
+        w.st_e[0] = w.gb[w.rq_u[j]];
+        while (sp > 0) {
+          const uint32_t u = w.st_u[sp - 1], e = w.st_e[sp - 1];
+          if (e >= w.ge[u]) {
+            --sp;
+            continue;
+          }
+          w.st_e[sp - 1] = e + 1;
+          const uint32_t l = w.rq_l[e];
+          if (w.vis[l] == dfs) continue;
+          w.vis[l] = dfs;
+          if (w.g_tag[l] != tag) {
+            // free output: flip the path (every frame takes the edge it tried last)
+            for (uint32_t k = sp; k-- > 0;) {
+              const uint32_t uu = w.st_u[k], ee = w.st_e[k] - 1, ll = w.rq_l[ee];
+              w.g_tag[ll] = tag;
+              w.g_in[ll] = uu;
+              w.a_tag[uu] = tag;
+              w.a_l[uu] = ll;
+              w.a_v[uu] = w.rq_v[ee];
+            }
+            break;
+          }
+          if (sp <= U) {  // the output's input looks for another output
+            w.st_u[sp] = w.g_in[l];
+            w.st_e[sp] = w.gb[w.g_in[l]];
+            ++sp;
+          }
+        }
+      }
+    } else if (alloc == RT_PIM || alloc == RT_LOA) {
+      // requests per output (LOA's loneliness) and per input
+      for (uint32_t j = 0; j < nrq; ++j) w.ocnt[w.rq_l[j]] = 0;
+      for (uint32_t j = 0; j < nrq; ++j) {
+        const uint32_t u = w.rq_u[j], l = w.rq_l[j];
+        if (w.m_u[u] == rtag || w.m_l[l] == rtag) continue;
+        ++w.ocnt[l];
+        if (j == 0 || w.rq_u[j - 1] != u) w.gb[u] = j;
+        w.ge[u] = j + 1;
+      }
+      const uint64_t seed = now * 0x100000001b3ull + (uint64_t)rtag * 131u + it;
+      // outputs grant: PIM uniformly at random (reservoir over the
+      // requesters), LOA to the input with the fewest requests
+      for (uint32_t j = 0; j < nrq; ++j) {
+        const uint32_t u = w.rq_u[j], l = w.rq_l[j];
+        if (w.m_u[u] == rtag || w.m_l[l] == rtag) continue;
+        if (alloc == RT_PIM) {
+          const uint32_t n = w.g_tag[l] == tag ? w.g_key[l] + 1 : 1;
+          if (n == 1 || rt_hash(seed, (uint64_t)l << 20 | n) % n == 0) w.g_in[l] = u;
+          w.g_tag[l] = tag;
+          w.g_key[l] = n;
+        } else {
+          const uint32_t key = (w.ge[u] - w.gb[u]) << 20 | (uint32_t)((u + U - gptr[l] % U) % U);
+          if (w.g_tag[l] != tag || key < w.g_key[l]) {
+            w.g_tag[l] = tag;
+            w.g_key[l] = key;
+            w.g_in[l] = u;
+          }
+        }
+      }
+      // inputs accept: PIM at random among their grants, LOA the output
+      // with the fewest requests
+      for (uint32_t j = 0; j < nrq; ++j) {
+        const uint32_t u = w.rq_u[j], l = w.rq_l[j];
+        if (w.g_tag[l] != tag || w.g_in[l] != u) continue;
+        if (alloc == RT_PIM) {
+          const uint32_t n = w.a_tag[u] == tag ? w.a_key[u] + 1 : 1;
+          if (n == 1 || rt_hash(seed + 7, (uint64_t)u << 20 | n) % n == 0) {
+            w.a_l[u] = l;
+            w.a_v[u] = w.rq_v[j];
+          }
+          w.a_tag[u] = tag;
+          w.a_key[u] = n;
+        } else {
+          const uint32_t key = w.ocnt[l] << 20 | (uint32_t)((l + L - aptr[u] % L) % L);
+          if (w.a_tag[u] != tag || key < w.a_key[u]) {
+            w.a_tag[u] = tag;
+            w.a_key[u] = key;
+            w.a_l[u] = l;
+            w.a_v[u] = w.rq_v[j];
+          }
+        }
+      }
+    }
+  }
+
+  // ---- commit of a matched pair ----
+  // Input unit u sends the head flit of its chosen VC a_v[u] over link l:
+  // the pair is marked matched in this switch pass (`rtag`), the allocator
+  // pointers move past it (`move_ptrs`: iSLIP moves them on first-iteration
+  // matches only), then the switch traversal: the flit leaves its buffer, its
+  // credit goes into slot `cr` of the credit FIFO, the link carries it one
+  // flit per cycle; a head claims its downstream VC (an adaptive head moves
+  // one router on), a tail releases it; the tail of a packet's last hop is
+  // the packet's arrival.  Everything is done but the push into the
+  // downstream buffer: the result says where the flit went.
+  SIM_HDI RtHop traverse(uint32_t u, uint32_t l, uint32_t rtag, bool move_ptrs, uint64_t now, uint32_t cr) const {
+    w.m_u[u] = rtag;
+    w.m_l[l] = rtag;
+    if (move_ptrs) {
+      gptr[l] = (u + 1) % U;
+      aptr[u] = (l + 1) % L;
+    }
+    const uint32_t uv = u * V + w.a_v[u];
+    const uint32_t f = front(uv);
+    hv.vhead[uv] = (hv.vhead[uv] + 1) % B;
+    --hv.vcnt[uv];
+    w.crt[cr] = now + 1 + c.rt_credit;
+    w.crv[cr] = uv;
+    in_free[u] = now;
+    const uint32_t p = w.fpk[f], h = w.fhop[f], fi = f - w.fbase[p];
+    const bool head = fi == 0, tail = fi + 1 == w.nfl[p];
+    const uint64_t dep = link_next[l] > now + 1 ? link_next[l] : now + 1;
+    link_next[l] = dep + 1;
+    const uint64_t arr = dep + (w.lat ? w.lat[l] : chan);
+    if (h + 1 < w.nh[p]) {
+      const uint32_t du = N + l;
+      if (head) {
+        const uint32_t dv = free_vc(du, w.route[w.roff[p] + h] >> 31);
+        hv.vout[uv] = dv;
+        hv.vown[du * V + dv] = p;
+      }
+      if (adaptive && head) {
+        // the head moves one router along dimension port / 2
+        const uint32_t port = l % aP, dd = port / 2;
+        const uint32_t pw = (uint32_t)ipow(tk, dd);
+        w.pcur[p] = port % 2 == 0 ? w.pcur[p] + pw : w.pcur[p] - pw;
+      }
+      const uint32_t duv = du * V + hv.vout[uv];
+      ++hv.vocc[duv];
+      w.fhop[f] = h + 1;
+      w.ready[f] = arr + (head ? head_delay : body_delay);
+      if (tail) {
+        hv.vown[duv] = kRtNone;
+        hv.vout[uv] = kRtNone;
+      }
+      return {f, duv};
+    }
+    if (tail) w.tarr[p] = arr;
+    return {f, tail ? kRtDelivered : kRtEject};
+  }
+
+  // ---- event times ----
+  // the earliest time source s can inject (~0: its queue is empty)
+  SIM_HDI uint64_t source_time(uint32_t s) const {
+    const uint32_t p = w.shead[s];
+    if (p == kRtNone) return ~0ull;
+    return w.tinj[p] > inj_next[s] ? w.tinj[p] : inj_next[s];
+  }
+  // the earliest time after `now` a head flit of input unit u can move: when
+  // it is through its pipeline stages, the unit is free and its link within
+  // `slack` (~0: none; a time <= now is a flit waiting for a VC or a credit)
+  SIM_HDI uint64_t unit_time(uint32_t u, uint64_t now) const {
+    uint64_t m = ~0ull;
+    for (uint32_t v = 0; v < V; ++v) {
+      const uint32_t uv = u * V + v;
+      if (!hv.vcnt[uv]) continue;
+      const uint32_t f = front(uv);
+      uint64_t t = w.ready[f] > in_free[u] ? w.ready[f] : in_free[u];
+      const uint32_t l = w.route[w.roff[w.fpk[f]] + w.fhop[f]] & 0x7fffffffu;
+      if (l < L && link_next[l] > 1 + slack && link_next[l] - 1 - slack > t) t = link_next[l] - 1 - slack;
+      if (t > now && t < m) m = t;
+    }
+    return m;
+  }
+  // a packet a routing deadlock left undelivered at `now`, the last event:
+  // its uncontended traversal from then
+  SIM_HDI void deadlock_arrival(uint32_t p, uint64_t now) const {
+    if (!w.tarr[p]) w.tarr[p] = (now > w.tinj[p] ? now : w.tinj[p]) + rt_uncontended(c, w.nh[p], w.nfl[p]);
+  }
+};
+
+// ---- the serial driver ----
+// Simulate the `np` packets already in w (src, dst, nfl, tinj) through one
+// subnet whose persistent state is `st` (rt_state_words); fills w.tarr (the
+// tail flit's arrival, icnt cycles) and returns the number of packets that
+// could not be delivered (a routing deadlock: they get their uncontended
+// traversal after the last delivery).  Single-threaded: plain loops over the
+// source list, the active list, the request list and the credit FIFO.
+SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, uint32_t np,
+                             uint64_t* act = nullptr) {
+  const RtCtx<RtHot<uint32_t*>> cx(c, d, st, w, RtHot<uint32_t*>{w.vhead, w.vcnt, w.vown, w.vout, w.vocc});
+  const RtHot<uint32_t*>& hv = cx.hv;  // the hot words: the driver and RtCtx go through the same view
+  const uint32_t V = cx.V, B = cx.B, N = cx.N, L = cx.L, U = cx.U;
+  uint64_t *const gptr = cx.gptr, *const in_free = cx.in_free, *const aptr = cx.aptr, *const inj_next = cx.inj_next;
+  // ---- routes, flits, source queues (injection order: time, then packet) ----
+  for (uint32_t s = 0; s < N; ++s) {
+    w.shead[s] = w.stail[s] = kRtNone;
+    w.sfl[s] = 0;
+    w.svc[s] = kRtNone;
+    w.sflag[s] = 0;
+  }
+  uint32_t nf = 0, nsrc = 0;
+  for (uint32_t p = 0; p < np; ++p) {
+    w.fbase[p] = nf;
+    cx.init_packet(p, nf);
+    nf += w.nfl[p];
+    cx.link_source(p, nsrc);
+  }
   for (uint64_t i = 0; i < (uint64_t)U * V; ++i) {
-    w.vhead[i] = w.vcnt[i] = w.vocc[i] = 0;
-    w.vown[i] = w.vout[i] = kRtNone;
+    hv.vhead[i] = hv.vcnt[i] = hv.vocc[i] = 0;
+    hv.vown[i] = hv.vout[i] = kRtNone;
   }
   for (uint32_t u = 0; u < U; ++u) {
     w.actf[u] = 0;
@@ -370,65 +757,16 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       w.act[nact++] = u;
     }
   };
-  auto push = [&](uint32_t uv, uint32_t f) {
-    w.ring[(uint64_t)uv * B + (w.vhead[uv] + w.vcnt[uv]) % B] = f;
-    ++w.vcnt[uv];
-  };
-  // a free VC with room on downstream unit du (kRtNone if none)
-  // VC class: dateline (torus) 0 lower / 1 upper half; adaptive 0 escape VC
-  // / 1 adaptive VCs; 2 any
-  auto free_vc = [&](uint32_t du, uint32_t cls) -> uint32_t {
-    uint32_t v0 = 0, v1 = V;
-    if (cls < 2 && (dateline || valiant)) {
-      v0 = cls ? V / 2 : 0;
-      v1 = cls ? V : V / 2;
-    } else if (cls < 2 && adaptive) {
-      v0 = cls ? 1 : 0;
-      v1 = cls ? V : 1;
-    }
-    for (uint32_t v = v0; v < v1; ++v) {
-      const uint32_t i = du * V + v;
-      if (w.vown[i] == kRtNone && w.vocc[i] < B) return v;
-    }
-    return kRtNone;
-  };
-  // the head of packet p chooses its next link: the productive direction
-  // whose downstream unit has an adaptive VC with the most free slots
-  // (lowest dimension on ties), else the dimension-order link if its escape
-  // VC is free; kRtUnrouted if blocked.  Returns link | class << 31.
-  auto adapt_choice = [&](uint32_t p) -> uint32_t {
-    const uint32_t cur = w.pcur[p], dst = w.dst[p] / aconc;
-    if (cur == dst) return cur * aP + 2 * tn + w.dst[p] % aconc;  // ejection
-    uint32_t best = kRtUnrouted, best_free = 0, esc = kRtUnrouted;
-    uint64_t pw = 1;
-    for (uint32_t dd = 0; dd < tn; ++dd, pw *= tk) {
-      const uint32_t x = (uint32_t)((cur / pw) % tk), y = (uint32_t)((dst / pw) % tk);
-      if (x == y) continue;
-      const uint32_t l = cur * aP + 2 * dd + (y > x ? 0u : 1u), du = N + l;
-      if (esc == kRtUnrouted) esc = l;
-      for (uint32_t v = 1; v < V; ++v) {
-        const uint32_t i = du * V + v;
-        if (w.vown[i] == kRtNone && w.vocc[i] < B && B - w.vocc[i] > best_free) {
-          best_free = B - w.vocc[i];
-          best = l;
-        }
-      }
-    }
-    if (best != kRtUnrouted) return best | 1u << 31;
-    if (esc != kRtUnrouted && free_vc(N + esc, 0) != kRtNone) return esc;
-    return kRtUnrouted;
-  };
   uint64_t now = ~0ull;
   for (uint32_t i = 0; i < nsrc; ++i) {
-    const uint32_t s = w.slist[i];
-    const uint64_t t = w.tinj[w.shead[s]] > inj_next[s] ? w.tinj[w.shead[s]] : inj_next[s];
+    const uint64_t t = cx.source_time(w.slist[i]);
     if (t < now) now = t;
   }
   while (remaining > 0) {
     bool progress = false;
     // ---- credits that reach their upstream this cycle ----
     while (cr_r < cr_w && w.crt[cr_r] <= now) {
-      --w.vocc[w.crv[cr_r]];
+      --hv.vocc[w.crv[cr_r]];
       if (act) ++act[RT_ACT_CREDIT];
       ++cr_r;
       progress = true;
@@ -446,24 +784,24 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
         w.slist[keep++] = s;
         if (now < w.tinj[p] || now < inj_next[s]) continue;
         if (w.svc[s] == kRtNone) {
-          const uint32_t v = free_vc(s, 2);
+          const uint32_t v = cx.free_vc(s, 2);
           if (v == kRtNone) continue;
           w.svc[s] = v;
-          w.vown[s * V + v] = p;
+          hv.vown[s * V + v] = p;
         }
         const uint32_t uv = s * V + w.svc[s];
-        if (w.vocc[uv] >= B) continue;
+        if (hv.vocc[uv] >= B) continue;
         const uint32_t i_f = w.sfl[s], f = w.fbase[p] + i_f;
-        push(uv, f);
+        cx.push(uv, f);
         if (act) ++act[RT_ACT_BUF_WRITE];
-        ++w.vocc[uv];
+        ++hv.vocc[uv];
         w.fhop[f] = 0;
-        w.ready[f] = now + (w.inj_lat ? w.inj_lat[s] : chan) + (i_f == 0 ? head_delay : body_delay);
+        w.ready[f] = now + (w.inj_lat ? w.inj_lat[s] : cx.chan) + (i_f == 0 ? cx.head_delay : cx.body_delay);
         activate(s);
         inj_next[s] = now + 1;
         progress = true;
         if (++w.sfl[s] == w.nfl[p]) {
-          w.vown[uv] = kRtNone;
+          hv.vown[uv] = kRtNone;
           w.sfl[s] = 0;
           w.svc[s] = kRtNone;
           w.shead[s] = w.next[p];
@@ -484,28 +822,9 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
         if (now < in_free[u]) continue;  // an earlier epoch's flits still leaving (FIFO)
         const uint32_t first = nrq;
         for (uint32_t v = 0; v < V; ++v) {
-          const uint32_t uv = u * V + v;
-          if (!w.vcnt[uv]) continue;
-          const uint32_t f = w.ring[(uint64_t)uv * B + w.vhead[uv]];
-          if (w.ready[f] > now) continue;
-          const uint32_t p = w.fpk[f], h = w.fhop[f];
-          if (adaptive && f == w.fbase[p]) {
-            const uint32_t ch = adapt_choice(p);
-            if (ch == kRtUnrouted) continue;
-            w.route[w.roff[p] + h] = ch;
-          }
-          const uint32_t rl = w.route[w.roff[p] + h], l = rl & 0x7fffffffu;
-          const bool last = h + 1 >= w.nh[p];
-          if (!last) {
-            const uint32_t du = N + l;
-            if (f == w.fbase[p]) {
-              if (free_vc(du, rl >> 31) == kRtNone) continue;
-            } else if (w.vocc[du * V + w.vout[uv]] >= B) {
-              continue;
-            }
-          }
-          const uint64_t dep = link_next[l] > now + 1 ? link_next[l] : now + 1;
-          if (dep > now + 1 + slack) continue;
+          uint32_t f;
+          const uint32_t l = cx.request(u, v, now, f);
+          if (l == kRtNone) continue;
           uint32_t j = first;
           while (j < nrq && w.rq_l[j] != l) ++j;
           if (j == nrq) {
@@ -513,9 +832,8 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
             w.rq_v[nrq] = v;
             w.rq_l[nrq] = l;
             ++nrq;
-          } else {
-            const uint32_t g = w.ring[(uint64_t)(u * V + w.rq_v[j]) * B + w.vhead[u * V + w.rq_v[j]]];
-            if (w.ready[f] < w.ready[g]) w.rq_v[j] = v;
+          } else if (cx.older(f, u, w.rq_v[j])) {
+            w.rq_v[j] = v;
           }
         }
       }
@@ -525,128 +843,14 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       }
       if (!nrq) continue;
       // matching
-      for (uint32_t it = 0; it < iters; ++it) {
+      for (uint32_t it = 0; it < cx.iters; ++it) {
         ++tag;
         bool any = false;
-        if (c.rt_alloc == RT_WAVEFRONT || c.rt_alloc == RT_MAX_SIZE) {
-          // one-shot allocators: a single iteration finds the whole matching
-          if (it > 0) break;
-          if (c.rt_alloc == RT_WAVEFRONT) {
-            // diagonal (u + l) mod n of the request matrix, from the priority
-            // diagonal of this cycle; within a diagonal no two cells share a
-            // row or a column
-            const uint32_t n = U > L ? U : L, pd = (uint32_t)(now % n);
-            for (uint32_t j = 0; j < nrq; ++j) {
-              w.rq_k[j] = (w.rq_u[j] + w.rq_l[j] + n - pd) % n;
-              uint32_t q = j;  // insertion into the order by (diagonal, request)
-              while (q > 0 && w.rq_k[w.rq_o[q - 1]] > w.rq_k[j]) {
-                w.rq_o[q] = w.rq_o[q - 1];
-                --q;
-              }
-              w.rq_o[q] = j;
-            }
-            for (uint32_t q = 0; q < nrq; ++q) {
-              const uint32_t j = w.rq_o[q], u = w.rq_u[j], l = w.rq_l[j];
-              if (w.a_tag[u] == tag || w.g_tag[l] == tag) continue;
-              w.a_tag[u] = w.g_tag[l] = tag;
-              w.a_l[u] = l;
-              w.a_v[u] = w.rq_v[j];
-              w.g_in[l] = u;
-            }
-          } else {
-            // maximum matching: an augmenting path from every input in turn
-            // (its requests are contiguous in the request list)
-            for (uint32_t j = 0; j < nrq; ++j) {
-              if (j == 0 || w.rq_u[j - 1] != w.rq_u[j]) w.gb[w.rq_u[j]] = j;
-              w.ge[w.rq_u[j]] = j + 1;
-            }
-            for (uint32_t j = 0; j < nrq; j = w.ge[w.rq_u[j]]) {
-              ++dfs;
-              uint32_t sp = 1;
-              w.st_u[0] = w.rq_u[j];
-              w.st_e[0] = w.gb[w.rq_u[j]];
-              while (sp > 0) {
-                const uint32_t u = w.st_u[sp - 1], e = w.st_e[sp - 1];
-                if (e >= w.ge[u]) {
-                  --sp;
-                  continue;
-                }
-                w.st_e[sp - 1] = e + 1;
-                const uint32_t l = w.rq_l[e];
-                if (w.vis[l] == dfs) continue;
-                w.vis[l] = dfs;
-                if (w.g_tag[l] != tag) {
-                  // free output: flip the path (every frame takes the edge it tried last)
-                  for (uint32_t k = sp; k-- > 0;) {
-                    const uint32_t uu = w.st_u[k], ee = w.st_e[k] - 1, ll = w.rq_l[ee];
-                    w.g_tag[ll] = tag;
-                    w.g_in[ll] = uu;
-                    w.a_tag[uu] = tag;
-                    w.a_l[uu] = ll;
-                    w.a_v[uu] = w.rq_v[ee];
-                  }
-                  break;
-                }
-                if (sp <= U) {  // the output's input looks for another output
-                  w.st_u[sp] = w.g_in[l];
-                  w.st_e[sp] = w.gb[w.g_in[l]];
-                  ++sp;
-                }
-              }
-            }
-          }
-        } else if (c.rt_alloc == RT_PIM || c.rt_alloc == RT_LOA) {
-          // requests per output (LOA's loneliness) and per input
-          for (uint32_t j = 0; j < nrq; ++j) w.ocnt[w.rq_l[j]] = 0;
-          for (uint32_t j = 0; j < nrq; ++j) {
-            const uint32_t u = w.rq_u[j], l = w.rq_l[j];
-            if (w.m_u[u] == rtag || w.m_l[l] == rtag) continue;
-            ++w.ocnt[l];
-            if (j == 0 || w.rq_u[j - 1] != u) w.gb[u] = j;
-            w.ge[u] = j + 1;
-          }
-          const uint64_t seed = now * 0x100000001b3ull + (uint64_t)rtag * 131u + it;
-          // outputs grant: PIM uniformly at random (reservoir over the
-          // requesters), LOA to the input with the fewest requests
-          for (uint32_t j = 0; j < nrq; ++j) {
-            const uint32_t u = w.rq_u[j], l = w.rq_l[j];
-            if (w.m_u[u] == rtag || w.m_l[l] == rtag) continue;
-            if (c.rt_alloc == RT_PIM) {
-              const uint32_t n = w.g_tag[l] == tag ? w.g_key[l] + 1 : 1;
-              if (n == 1 || rt_hash(seed, (uint64_t)l << 20 | n) % n == 0) w.g_in[l] = u;
-              w.g_tag[l] = tag;
-              w.g_key[l] = n;
-            } else {
-              const uint32_t key = (w.ge[u] - w.gb[u]) << 20 | (uint32_t)((u + U - gptr[l] % U) % U);
-              if (w.g_tag[l] != tag || key < w.g_key[l]) {
-                w.g_tag[l] = tag;
-                w.g_key[l] = key;
-                w.g_in[l] = u;
-              }
-            }
-          }
-          for (uint32_t j = 0; j < nrq; ++j) {
-            const uint32_t u = w.rq_u[j], l = w.rq_l[j];
-            if (w.g_tag[l] != tag || w.g_in[l] != u) continue;
-            if (c.rt_alloc == RT_PIM) {
-              const uint32_t n = w.a_tag[u] == tag ? w.a_key[u] + 1 : 1;
-              if (n == 1 || rt_hash(seed + 7, (uint64_t)u << 20 | n) % n == 0) {
-                w.a_l[u] = l;
-                w.a_v[u] = w.rq_v[j];
-              }
-              w.a_tag[u] = tag;
-              w.a_key[u] = n;
-            } else {
-              const uint32_t key = w.ocnt[l] << 20 | (uint32_t)((l + L - aptr[u] % L) % L);
-              if (w.a_tag[u] != tag || key < w.a_key[u]) {
-                w.a_tag[u] = tag;
-                w.a_key[u] = key;
-                w.a_l[u] = l;
-                w.a_v[u] = w.rq_v[j];
-              }
-            }
-          }
-        } else if (c.rt_alloc == RT_SEP_INPUT_FIRST) {
+        // one-shot allocators: a single iteration finds the whole matching
+        if (cx.one_shot_alloc() && it > 0) break;
+        if (cx.ordered_alloc()) {
+          cx.allocate_ordered(nrq, now, tag, rtag, it, dfs);
+        } else if (cx.alloc == RT_SEP_INPUT_FIRST) {
           // inputs choose first (accept pointer), then outputs (grant pointer)
           for (uint32_t j = 0; j < nrq; ++j) {
             const uint32_t u = w.rq_u[j], l = w.rq_l[j];
@@ -698,59 +902,18 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
           const uint32_t u = w.rq_u[j], l = w.rq_l[j];
           if (w.a_tag[u] != tag || w.a_l[u] != l || w.g_tag[l] != tag || w.g_in[l] != u) continue;
           if (w.m_u[u] == rtag || w.m_l[l] == rtag) continue;
-          w.m_u[u] = rtag;
-          w.m_l[l] = rtag;
           any = true;
           progress = true;
-          // iSLIP moves its pointers on first-iteration matches only
-          if (c.rt_alloc != RT_ISLIP || it == 0) {
-            gptr[l] = (u + 1) % U;
-            aptr[u] = (l + 1) % L;
-          }
-          // switch traversal of the head flit of VC (u, a_v[u])
-          const uint32_t uv = u * V + w.a_v[u];
-          const uint32_t f = w.ring[(uint64_t)uv * B + w.vhead[uv]];
-          w.vhead[uv] = (w.vhead[uv] + 1) % B;
-          --w.vcnt[uv];
-          w.crt[cr_w] = now + 1 + c.rt_credit;
-          w.crv[cr_w] = uv;
-          ++cr_w;
-          in_free[u] = now;
-          const uint32_t p = w.fpk[f], h = w.fhop[f], fi = f - w.fbase[p];
-          const bool head = fi == 0, tail = fi + 1 == w.nfl[p];
-          const uint64_t dep = link_next[l] > now + 1 ? link_next[l] : now + 1;
-          link_next[l] = dep + 1;
+          const RtHop hop = cx.traverse(u, l, rtag, cx.alloc != RT_ISLIP || it == 0, now, cr_w++);
           if (act) {
             ++act[RT_ACT_BUF_READ];
-            ++act[h + 1 < w.nh[p] ? RT_ACT_LINK : RT_ACT_EJECT];
+            ++act[hop.to < kRtDelivered ? RT_ACT_LINK : RT_ACT_EJECT];
           }
-          const uint64_t arr = dep + (w.lat ? w.lat[l] : chan);
-          if (h + 1 < w.nh[p]) {
-            const uint32_t du = N + l;
-            if (head) {
-              const uint32_t dv = free_vc(du, w.route[w.roff[p] + h] >> 31);
-              w.vout[uv] = dv;
-              w.vown[du * V + dv] = p;
-            }
-            if (adaptive && head) {
-              // the head moves one router along dimension port / 2
-              const uint32_t port = l % aP, dd = port / 2;
-              const uint32_t pw = (uint32_t)ipow(tk, dd);
-              w.pcur[p] = port % 2 == 0 ? w.pcur[p] + pw : w.pcur[p] - pw;
-            }
-            const uint32_t duv = du * V + w.vout[uv];
-            ++w.vocc[duv];
-            push(duv, f);
+          if (hop.to < kRtDelivered) {
+            cx.push(hop.to, hop.f);
             if (act) ++act[RT_ACT_BUF_WRITE];
-            w.fhop[f] = h + 1;
-            w.ready[f] = arr + (head ? head_delay : body_delay);
-            activate(du);
-            if (tail) {
-              w.vown[duv] = kRtNone;
-              w.vout[uv] = kRtNone;
-            }
-          } else if (tail) {
-            w.tarr[p] = arr;
+            activate(N + l);
+          } else if (hop.to == kRtDelivered) {
             --remaining;
           }
         }
@@ -763,7 +926,7 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       for (uint32_t i = 0; i < nact; ++i) {
         const uint32_t u = w.act[i];
         uint32_t cnt = 0;
-        for (uint32_t v = 0; v < V; ++v) cnt += w.vcnt[u * V + v];
+        for (uint32_t v = 0; v < V; ++v) cnt += hv.vcnt[u * V + v];
         if (cnt) {
           w.act[keep++] = u;
         } else {
@@ -780,32 +943,19 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
     } else {
       if (cr_r < cr_w) nxt = w.crt[cr_r];
       for (uint32_t i = 0; i < nsrc; ++i) {
-        const uint32_t s = w.slist[i], p = w.shead[s];
-        if (p == kRtNone) continue;
-        const uint64_t t = w.tinj[p] > inj_next[s] ? w.tinj[p] : inj_next[s];
+        const uint64_t t = cx.source_time(w.slist[i]);
         if (t > now && t < nxt) nxt = t;  // (t <= now: waiting for a credit)
       }
       for (uint32_t i = 0; i < nact; ++i) {
-        const uint32_t u = w.act[i];
-        for (uint32_t v = 0; v < V; ++v) {
-          const uint32_t uv = u * V + v;
-          if (!w.vcnt[uv]) continue;
-          const uint32_t f = w.ring[(uint64_t)uv * B + w.vhead[uv]];
-          uint64_t t = w.ready[f] > in_free[u] ? w.ready[f] : in_free[u];
-          const uint32_t l = w.route[w.roff[w.fpk[f]] + w.fhop[f]] & 0x7fffffffu;
-          if (l < L && link_next[l] > 1 + slack && link_next[l] - 1 - slack > t) t = link_next[l] - 1 - slack;
-          if (t > now && t < nxt) nxt = t;  // (t <= now: waiting for a VC or a credit)
-        }
+        const uint64_t t = cx.unit_time(w.act[i], now);
+        if (t < nxt) nxt = t;
       }
     }
     if (nxt == ~0ull) break;  // nothing can ever move: deadlock
     now = nxt;
   }
-  if (remaining) {
-    // deadlocked packets: their uncontended traversal after the last event
-    for (uint32_t p = 0; p < np; ++p)
-      if (!w.tarr[p]) w.tarr[p] = (now > w.tinj[p] ? now : w.tinj[p]) + rt_uncontended(c, w.nh[p], w.nfl[p]);
-  }
+  if (remaining)
+    for (uint32_t p = 0; p < np; ++p) cx.deadlock_arrival(p, now);
   return remaining;
 }
 
@@ -839,6 +989,50 @@ SIM_HDI RtDims rt_epoch_dims(const SimCfg& c, uint32_t cap_req, uint32_t cap_rep
   return rt_dims(c, c.n_sm * c.n_subpart * cap, rt_flits(c, kRtMaxPktBytes));
 }
 
+// ---- the epoch pass's packets: shared by rt_epoch_run and rt_epoch_run_par ----
+// The packets of mailbox cell `cell` of direction `dir` (0 request, 1 reply)
+// go from node a to node b, between SM sm and L2 sub-partition sub
+struct RtCell {
+  uint32_t a, b, sm, sub;
+};
+
+SIM_HDI RtCell rt_cell(const SimCfg& c, uint32_t dir, uint32_t cell) {
+  const uint32_t cpc = c.cores_per_cluster ? c.cores_per_cluster : 1;
+  RtCell ce;
+  if (dir == 0) {  // request: SM (cell % n_sm) -> sub-partition (cell / n_sm)
+    ce.sm = cell % c.n_sm;
+    ce.sub = cell / c.n_sm;
+    ce.a = ce.sm / cpc;
+    ce.b = c.n_clusters + ce.sub;
+  } else {  // reply: sub-partition (cell % n_subpart) -> SM (cell / n_subpart)
+    ce.sub = cell % c.n_subpart;
+    ce.sm = cell / c.n_subpart;
+    ce.a = c.n_clusters + ce.sub;
+    ce.b = ce.sm / cpc;
+  }
+  return ce;
+}
+
+// packet i of a pass: mailbox packet p of box slot `slot`, whose cell is ce
+// and whose uncontended latency is lat_fs (icnt_pkt_lat_fs of the cell);
+// nfl_max = rt_flits(c, kRtMaxPktBytes), the flits the scratch holds per packet
+SIM_HDI void rt_fill_packet(const SimCfg& c, const RtWork& w, uint32_t i, const Pkt& p, const RtCell& ce,
+                            uint64_t lat_fs, uint32_t nfl_max, uint32_t slot) {
+  const uint64_t t0 = p.t > lat_fs ? p.t - lat_fs : 0;
+  const uint32_t nfl = rt_flits(c, p.size ? p.size : 1);
+  w.src[i] = ce.a;
+  w.dst[i] = ce.b;
+  w.nfl[i] = nfl < nfl_max ? nfl : nfl_max;
+  w.tinj[i] = fdiv(t0, c.dv_icnt);
+  w.bidx[i] = slot;
+}
+
+// packet i's delay over its uncontended traversal after the pass (icnt cycles)
+SIM_HDI uint64_t rt_packet_delay(const SimCfg& c, const RtWork& w, uint32_t i) {
+  const uint64_t base = w.tinj[i] + rt_uncontended(c, icnt_routers(c, w.src[i], w.dst[i]), w.nfl[i]);
+  return w.tarr[i] > base ? w.tarr[i] - base : 0;
+}
+
 // The epoch-boundary pass of -icnt_link_contention 2 over this epoch's
 // outboxes (same layout and packet order as icnt_contend): `st` holds both
 // subnets' persistent state then the two statistics words; `scratch` holds
@@ -850,7 +1044,7 @@ SIM_HDN void rt_epoch_run(const SimCfg& c, Pkt* box_req, const uint32_t* cnt_req
   rt_carve(d, scratch, &w);
   uint64_t* stat = st + 2 * rt_state_words(d);
   const uint32_t ncell = c.n_sm * c.n_subpart;
-  const uint32_t cpc = c.cores_per_cluster ? c.cores_per_cluster : 1;
+  const uint32_t nfl_max = rt_flits(c, kRtMaxPktBytes);
   for (int dir = 0; dir < 2; ++dir) {
     const uint32_t* cnt = dir == 0 ? cnt_req : cnt_rep;
     Pkt* box = dir == 0 ? box_req : box_rep;
@@ -858,28 +1052,11 @@ SIM_HDN void rt_epoch_run(const SimCfg& c, Pkt* box_req, const uint32_t* cnt_req
     // the packets in cell order (their box slots in w.bidx)
     uint32_t np = 0;
     for (uint32_t cell = 0; cell < ncell; ++cell) {
+      if (!cnt[cell]) continue;
+      const RtCell ce = rt_cell(c, dir, cell);
+      const uint64_t lat = icnt_pkt_lat_fs(c, ce.sm, ce.sub);
       for (uint32_t j = 0; j < cnt[cell]; ++j) {
-        const Pkt& p = box[(uint64_t)cell * cap + j];
-        uint32_t a, b, sm, sub;
-        if (dir == 0) {  // request: SM (cell % n_sm) -> sub-partition (cell / n_sm)
-          sm = cell % c.n_sm;
-          sub = cell / c.n_sm;
-          a = sm / cpc;
-          b = c.n_clusters + sub;
-        } else {  // reply: sub-partition (cell % n_subpart) -> SM (cell / n_subpart)
-          sub = cell % c.n_subpart;
-          sm = cell / c.n_subpart;
-          a = c.n_clusters + sub;
-          b = sm / cpc;
-        }
-        const uint64_t lat = icnt_pkt_lat_fs(c, sm, sub);
-        const uint64_t t0 = p.t > lat ? p.t - lat : 0;
-        w.src[np] = a;
-        w.dst[np] = b;
-        const uint32_t nfl = rt_flits(c, p.size ? p.size : 1), nfl_max = rt_flits(c, kRtMaxPktBytes);
-        w.nfl[np] = nfl < nfl_max ? nfl : nfl_max;  // the scratch holds nfl_max flits per packet
-        w.tinj[np] = fdiv(t0, c.dv_icnt);
-        w.bidx[np] = cell * cap + j;
+        rt_fill_packet(c, w, np, box[(uint64_t)cell * cap + j], ce, lat, nfl_max, cell * cap + j);
         ++np;
       }
     }
@@ -887,8 +1064,7 @@ SIM_HDN void rt_epoch_run(const SimCfg& c, Pkt* box_req, const uint32_t* cnt_req
     const uint32_t lost = rt_simulate(c, d, st + (uint64_t)dir * rt_state_words(d), w, np);
     uint64_t delayed = 0, wait = 0;
     for (uint32_t i = 0; i < np; ++i) {
-      const uint64_t base = w.tinj[i] + rt_uncontended(c, icnt_routers(c, w.src[i], w.dst[i]), w.nfl[i]);
-      const uint64_t D = w.tarr[i] > base ? w.tarr[i] - base : 0;
+      const uint64_t D = rt_packet_delay(c, w, i);
       if (D) {
         ++delayed;
         wait += D;

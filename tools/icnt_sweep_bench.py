@@ -57,8 +57,8 @@ def worker(a) -> int:
             return 2
         mod.icnt_open_loop_batch(text, pts[:1], engine="gpu")  # the runtime's start-up is not the sweep's time
     t0 = time.perf_counter()
-    if a.worker == "cpu":
-        res = [mod.icnt_open_loop_batch(text, [p], engine="cpu")[0] for p in pts]  # the single-threaded host loop
+    if a.worker != "gpu":  # the single-threaded host loop (cpu-par: the lane-parallel pass on one lane)
+        res = [mod.icnt_open_loop_batch(text, [p], engine=a.worker)[0] for p in pts]
     else:
         res = mod.icnt_open_loop_batch(text, pts, engine="gpu", mem_budget_mb=a.mem_budget_mb)
     rec["seconds"] = time.perf_counter() - t0
@@ -83,7 +83,7 @@ def main(argv=None) -> int:
     ap.add_argument("--seeds", type=int, default=4)
     ap.add_argument("--mem-budget-mb", type=int, default=0)
     ap.add_argument("--gpu-timeout", type=int, default=900, help="seconds the GPU step may take")
-    ap.add_argument("--worker", choices=("cpu", "gpu"), help=argparse.SUPPRESS)
+    ap.add_argument("--worker", choices=("cpu", "cpu-par", "gpu"), help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.worker:
         return worker(a)

@@ -90,7 +90,8 @@ def ab(mod, args, kl, engine, reps):
     wp = [r["wall_s"] for r in runs if r["mode"] == "par"]
     ms, mp = statistics.median(ws), statistics.median(wp)
     return dict(engine=engine, variant=base["variant"], blocks=base["blocks"], tot_cycle=base["result"][0],
-                link_stats=dict(zip(STAT_KEYS, base["result"][1:])), results_and_snapshots_equal=equal,
+                link_stats=dict(zip(STAT_KEYS, base["result"][1:])), snapshot_sha256=base["snapshot_sha256"],
+                results_and_snapshots_equal=equal,
                 router_pass=[r for r in runs if r["mode"] == "par"][0]["router_pass"],
                 serial_wall_s=ws, par_wall_s=wp, serial_median_s=round(ms, 4), par_median_s=round(mp, 4),
                 serial_spread=round((max(ws) - min(ws)) / ms, 4), par_spread=round((max(wp) - min(wp)) / mp, 4),
