@@ -555,6 +555,99 @@ PYBIND11_MODULE(_asim, m) {
           return ingest_cmp(k, c, device);
         },
         py::arg("insts"), py::arg("args"), py::arg("device") = 0);
+  // the same instructions, returning what the ingest computed instead of a
+  // verdict.  The address field is the list of the active lanes' addresses or
+  // a (base, stride) tuple (TMem without a list: base + stride * rank).  Per
+  // instruction (final space, final width, [(line, sectors, bytes, bank)]):
+  // "host" from coalesce_kernel; with device >= 0 and a usable device also
+  // "device" from gpu_coalesce_kernel and "on_device" (1: the matrix cores
+  // produced it, 0: the host fallback).  device -1 touches no GPU.
+  m.def("ingest_lanes_result",
+        [](const py::list& ins, const std::vector<std::string>& args, int device) {
+          SimCfg c = cfg_from_args(args);
+          HostKernel k;
+          k.h.name = "ingest_lanes";
+          k.h.warp_size = c.warp_size ? c.warp_size : 32;
+          k.n_cta = 1;
+          k.warps_per_cta = 1;
+          size_t idx = 0;
+          for (const py::handle& h : ins) {
+            const std::string at = " (instruction " + std::to_string(idx++) + ")";
+            const py::tuple t = py::cast<py::tuple>(h);
+            if (t.size() != 5) throw py::value_error("(space, width, mask, addresses, opcode) expected" + at);
+            const std::string space = py::cast<std::string>(t[0]);
+            if (space != "shared" && space != "global") throw py::value_error("space is 'shared' or 'global'" + at);
+            const uint64_t width = py::cast<uint64_t>(t[1]);
+            if (width > 255) throw py::value_error("width above 255 bytes per lane" + at);
+            const std::string op = py::cast<std::string>(t[4]);
+            TInst in{};
+            in.cls = OC_LOAD;
+            in.space = space == "shared" ? S_SHARED : S_GLOBAL;
+            in.width = (uint8_t)width;
+            in.mask = py::cast<uint64_t>(t[2]);
+            if (!op.empty()) in.opcode = decode_opcode(op, 950).opcode;
+            TMem m{};
+            if (py::isinstance<py::tuple>(t[3])) {
+              const py::tuple bs = py::cast<py::tuple>(t[3]);
+              if (bs.size() != 2) throw py::value_error("(base, stride) expected" + at);
+              const py::int_ stride = py::cast<py::int_>(bs[1]);
+              const long long sv = PyLong_AsLongLong(stride.ptr());
+              if (PyErr_Occurred()) {
+                PyErr_Clear();
+                throw py::value_error("stride outside int32" + at);
+              }
+              if (sv < INT32_MIN || sv > INT32_MAX) throw py::value_error("stride outside int32" + at);
+              m.base = py::cast<uint64_t>(bs[0]);
+              m.stride = (int32_t)sv;
+              m.list = kNoMem;
+            } else {
+              const std::vector<uint64_t> a = py::cast<std::vector<uint64_t>>(t[3]);
+              if ((size_t)__builtin_popcountll(in.mask) != a.size())
+                throw py::value_error("one address per active lane" + at);
+              m.list = (uint32_t)k.addrs.size();
+              k.addrs.insert(k.addrs.end(), a.begin(), a.end());
+              m.base = a.empty() ? 0 : a[0];
+            }
+            in.mem = (uint32_t)k.mems.size();
+            k.mems.push_back(m);
+            k.insts.push_back(in);
+          }
+          k.streams.push_back(WStream{0, (uint32_t)k.insts.size()});
+          auto results = [](const ReadyKernel& r) {
+            py::list out;
+            for (const TInst& in : r.insts) {
+              py::list acc;
+              if (in.mem != kNoMem)
+                for (uint32_t q = 0; q < in.width; ++q) {
+                  const TAcc& a = r.accs.at((size_t)in.mem + q);
+                  acc.append(py::make_tuple(a.line, (int)a.sectors, (int)a.bytes, (int)a.bank));
+                }
+              out.append(py::make_tuple(in.space == S_SHARED ? "shared" : "global", (int)in.width, acc));
+            }
+            return out;
+          };
+          py::dict d;
+          d["host"] = results(coalesce_kernel(k, c));
+          d["ran"] = false;
+          if (device < 0) return d;
+          IngestStats st;
+          std::vector<uint8_t> where;
+          st.on_device = &where;
+          ReadyKernel g;
+          if (!gpu_coalesce_kernel(k, c, device, g, &st)) return d;
+          d["ran"] = true;
+          d["device"] = results(g);
+          py::list w;
+          for (uint8_t v : where) w.append((int)v);
+          d["on_device"] = w;
+          d["smem_device"] = st.smem_jobs;
+          d["smem_host"] = st.smem_host;
+          d["gmem_device"] = st.gmem_jobs;
+          d["gmem_host"] = st.gmem_host;
+          d["mfma"] = st.mfma;
+          return d;
+        },
+        py::arg("insts"), py::arg("args"), py::arg("device") = -1);
   // lane policy / register view unit check (csrc/engine/lane_check.h): the
   // SeqPar result always, the WavePar result when a device is visible
   m.def("lane_policy_check",

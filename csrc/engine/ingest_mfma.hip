@@ -466,6 +466,8 @@ bool gpu_coalesce_kernel(const HostKernel& k, const SimCfg& c, int device, Ready
   std::vector<uint64_t> lane(64);
   TAcc tmp[kMaxAccess];
   IngestStats loc;
+  std::vector<uint8_t>* where = st ? st->on_device : nullptr;
+  if (where) where->assign(n, 0);
   for (size_t i = 0; i < n; ++i) {
     TInst& in = r.insts[i];
     const uint32_t jb = job_of[i];
@@ -479,6 +481,7 @@ bool gpu_coalesce_kernel(const HostKernel& k, const SimCfg& c, int device, Ready
         if (jb != kNoMem && res[jb] != kFallback) {
           ++loc.smem_jobs;
           loc.mfma += nmf[jb];
+          if (where) (*where)[i] = 1;
           in.width = (uint8_t)std::min<uint32_t>(255, res[jb]);
         } else {
           ++loc.smem_host;
@@ -492,6 +495,7 @@ bool gpu_coalesce_kernel(const HostKernel& k, const SimCfg& c, int device, Ready
         if (res[jb] != kFallback) {
           ++loc.gmem_jobs;
           loc.mfma += nmf[jb];
+          if (where) (*where)[i] = 1;
           ingest_finish_global(in, dacc.data() + (res[jb] ? offs[jb] : 0), res[jb], r.accs);
         } else {
           ++loc.gmem_host;

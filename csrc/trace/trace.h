@@ -203,6 +203,9 @@ struct IngestStats {
   uint64_t gmem_jobs = 0, gmem_host = 0;  // global instructions: on the device / fell back to the host
   uint64_t mfma = 0;                      // matrix-core instructions issued
   double device_s = 0, total_s = 0;
+  // optional, filled per instruction of the kernel when set: 1 = coalesced on
+  // the device, 0 = on the host (fallback, or not a memory instruction)
+  std::vector<uint8_t>* on_device = nullptr;
 };
 // MI355X coalescer (bank-by-row and line-by-sector occupancy matrices on the
 // matrix cores); false when no HIP device / build
