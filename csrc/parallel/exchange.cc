@@ -370,16 +370,27 @@ py::dict exchange_run_device(py::object pgo, py::dict params, const std::string&
 // RCCL all-to-all of all ranks' send buffers, which a 1-rank group returns
 // unchanged (rank d reads its slot from s at [s][d]): the per-epoch work of an
 // 8-GPU run (one epoch kernel, one RCCL all-to-all, no host round trip) on one
-// MI355X.  Returns every rank's finish time (== linksim_run_local's).
+// MI355X.  Returns every rank's finish time (== linksim_run_local's) and final
+// counters.
+//
+// `record` (tests): one epoch per batch, and after every epoch kernel that
+// packed, every rank's send buffer comes back ("send": [epoch][src][dst][slot],
+// the first launch included); for each epoch that stopped for the overflow
+// exchange, its index among those ("spill_epochs"), every source's
+// per-destination overflow sizes ("spill_extra_words": [src][dst]) and
+// overflow words ("spill_extra": per source).
 py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes, int64_t root,
-                       std::vector<int64_t> starts, int64_t device, py::object loopback, int64_t batch_max) {
+                       std::vector<int64_t> starts, int64_t device, py::object loopback, int64_t batch_max,
+                       bool record) {
   c10::intrusive_ptr<c10d::ProcessGroup> pg;
   if (!loopback.is_none()) {
+    if (record) throw std::invalid_argument("dev_run_local: recording is not supported with a loopback group");
     pg = py::cast<c10::intrusive_ptr<c10d::ProcessGroup>>(loopback);
     if (pg->getSize() != 1) throw std::invalid_argument("dev_run_local: the loopback group must have one rank");
   }
   const int W = (int)starts.size();
   if (W < 1) throw std::invalid_argument("dev_run_local: no ranks");
+  if (record) batch_max = 1;
   CollSpec cs;
   cs.kind = coll_kind(kind);
   cs.bytes = (uint64_t)nbytes;
@@ -392,6 +403,10 @@ py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes,
   uint64_t exchanges = 0, polls = 0;
   double loop_s = 0;
   DevStates S;
+  std::vector<at::Tensor> rec_send;                        // per packed epoch: [W * W * slot]
+  std::vector<int64_t> rec_sp_epoch;                       // epochs that stopped for the overflow exchange
+  std::vector<std::vector<std::vector<int64_t>>> rec_ew;   // ... their [src][dst] overflow sizes
+  std::vector<std::vector<std::vector<int64_t>>> rec_xw;   // ... their overflow words per source
   {
     py::gil_scoped_release nogil;
     // a stream of our own; work the caller queued before is finished first
@@ -409,6 +424,7 @@ py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes,
     const auto t0c = std::chrono::steady_clock::now();
     dls_launch_epoch(S.base(), S.L, W, nullptr, 0, 0, d_send.data_ptr<int64_t>(), (int64_t)W * slot, nullptr, nullptr,
                      t0.data_ptr<int64_t>(), DLS_MODE_FIRST, stream);
+    if (record) rec_send.push_back(d_send.cpu());  // the copy is ordered on the stream and blocks the host
     auto exchange = [&] {
       if (pg)
         pg->alltoall_base(d_recv, d_send, all, all)->wait();
@@ -443,6 +459,11 @@ py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes,
             xw[s].assign(x.data_ptr<int64_t>(), x.data_ptr<int64_t>() + nx);
           }
         }
+        if (record) {
+          rec_sp_epoch.push_back((int64_t)rec_send.size() - 1);
+          rec_ew.push_back(ew);
+          rec_xw.push_back(xw);
+        }
         std::vector<int64_t> spill, off{0};
         for (int d = 0; d < W; ++d) {
           for (int s = 0; s < W; ++s) {
@@ -459,21 +480,36 @@ py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes,
                          d_send.data_ptr<int64_t>(), (int64_t)W * slot, d_sp.data_ptr<int64_t>(),
                          d_off.data_ptr<int64_t>(), nullptr, DLS_MODE_SPILL, stream);
         sync_stream((int)device);  // d_sp / d_off are freed on return
+        if (record) {
+          S.poll();
+          if (S.status() == DLS_RUN) rec_send.push_back(d_send.cpu());
+        }
         continue;
       }
       if (st != DLS_RUN) dls_fail(st);
+      if (record) rec_send.push_back(d_send.cpu());
       if (S.st(0).epochs == last_epochs) throw std::runtime_error("device epoch loop: no progress in a batch");
       last_epochs = S.st(0).epochs;
       b = std::min<int64_t>(2 * b, std::max<int64_t>(1, batch_max));
     }
     loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0c).count();
   }
-  std::vector<uint64_t> fin(W);
+  std::vector<uint64_t> fin(W), r_sent(W), r_packets(W), r_epochs(W), r_lds(W), r_hbm(W);
+  std::vector<int32_t> r_status(W);
+  std::vector<uint32_t> r_channels(W);
   uint64_t packets = 0;
   for (int r = 0; r < W; ++r) {
-    if (S.st(r).status != DLS_DONE) dls_fail(S.st(r).status);
-    fin[r] = S.st(r).finish_ps;
-    packets += S.st(r).packets;
+    const DlsState& s = S.st(r);
+    if (s.status != DLS_DONE) dls_fail(s.status);
+    fin[r] = s.finish_ps;
+    packets += s.packets;
+    r_sent[r] = s.sent;
+    r_packets[r] = s.packets;
+    r_epochs[r] = s.epochs;
+    r_status[r] = s.status;
+    r_channels[r] = (uint32_t)s.g.nch;
+    r_lds[r] = s.launches_lds;
+    r_hbm[r] = s.launches_hbm;
   }
   py::dict d;
   d["finish_ps"] = fin;
@@ -487,6 +523,23 @@ py::dict dev_run_local(py::dict params, const std::string& kind, int64_t nbytes,
   for (int i = 0; i < 7; ++i) prof.append((double)S.st(0).prof[i] / (double)std::max<uint64_t>(1, exchanges + 1));
   d["kernel_clocks_per_launch"] = prof;
   d["state_bytes_per_rank"] = (int64_t)S.L.bytes;
+  // every rank's final state
+  py::dict ranks;
+  ranks["finish_ps"] = fin;
+  ranks["sent"] = r_sent;
+  ranks["packets"] = r_packets;
+  ranks["epochs"] = r_epochs;
+  ranks["status"] = r_status;
+  ranks["channels"] = r_channels;
+  ranks["launches_lds"] = r_lds;
+  ranks["launches_hbm"] = r_hbm;
+  d["ranks"] = ranks;
+  if (record) {
+    d["send"] = at::stack(rec_send).view({(int64_t)rec_send.size(), W, W, slot});
+    d["spill_epochs"] = rec_sp_epoch;
+    d["spill_extra_words"] = rec_ew;
+    d["spill_extra"] = rec_xw;
+  }
   return d;
 }
 
@@ -511,5 +564,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("exchange_run_device", &asim::exchange_run_device, py::arg("group"), py::arg("params"), py::arg("kind"),
         py::arg("bytes"), py::arg("root"), py::arg("start_ps"), py::arg("device"), py::arg("batch_max") = 16);
   m.def("dev_run_local", &asim::dev_run_local, py::arg("params"), py::arg("kind"), py::arg("bytes"), py::arg("root"),
-        py::arg("starts"), py::arg("device"), py::arg("loopback") = py::none(), py::arg("batch_max") = 16);
+        py::arg("starts"), py::arg("device"), py::arg("loopback") = py::none(), py::arg("batch_max") = 16,
+        py::arg("record") = false);
 }

@@ -40,6 +40,9 @@ struct DlsState {
   int32_t k, hdr;
   int32_t pad;
   uint64_t prof[8];  // epoch kernel shader clocks, summed: load, unpack, pack, store | pack: emit, reductions, slots
+  // epoch launches that ran (no-op launches after the stop are not counted)
+  // with the links' heaps and packet buffers staged in LDS / left in HBM
+  uint64_t launches_lds, launches_hbm;
 };
 
 // byte offsets inside one rank's state block

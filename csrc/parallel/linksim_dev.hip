@@ -500,6 +500,7 @@ __global__ void __launch_bounds__(64) dls_epoch_kernel(char* states, DlsLayout L
       s.prof[5] += tp[1] - tp[0];
       s.prof[6] += tp[2] - tp[1];
     }
+    ++(in_lds ? s.launches_lds : s.launches_hbm);
   }
   __syncthreads();
   copy_out((GLB_AS int64_t*)G.s, (const LDS_AS int64_t*)lds, sizeof(DlsState) / 8, lane);

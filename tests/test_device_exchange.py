@@ -96,7 +96,7 @@ def _gloo_dev_worker(rank, world, port, cases, q):
                             timeout=datetime.timedelta(seconds=120))
     try:
         ex = collectives.PacketExchange(device=torch.device("cuda", 0))
-        out = [ex.run(p, kind, nbytes, 0, starts[rank])["finish_ps"] for p, kind, nbytes, starts in cases]
+        out = [ex.run(p, kind, nbytes, root, starts[rank])["finish_ps"] for p, kind, nbytes, starts, root in cases]
         q.put((rank, out, dict(ex.stats)))
     finally:
         dist.destroy_process_group()
@@ -113,6 +113,10 @@ def test_device_loop_multi_rank_over_gloo_device_tensors():
     _ext()
     cases = [c for c in CASES if len(c[3]) == 4] + [(PARAMS, "AllReduce", 4 << 20, [0, 700_000, 0, 13]),
                                                      (SMALL, "AllGather", 128 << 10, [0, 0, 0, 2_000_000])]
+    cases = [c + (0,) for c in cases]  # root
+    # two links for three peers: link 0 carries two destinations, 16 packets each in one epoch (overflow)
+    cases.append((dict(PARAMS, links=2, slice_bytes=256), "AllToAll", 16 << 10, [0, 0, 0, 0], 0))
+    cases.append((PARAMS, "Broadcast", 2 << 20, [0, 0, 500_000, 0], 2))
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -123,8 +127,8 @@ def test_device_loop_multi_rank_over_gloo_device_tensors():
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    for i, (p, kind, nbytes, starts) in enumerate(cases):
-        ref = collectives.emulate(p, kind, nbytes, starts)["finish_ps"]
+    for i, (p, kind, nbytes, starts, root) in enumerate(cases):
+        ref = collectives.emulate(p, kind, nbytes, starts, root)["finish_ps"]
         assert [res[r][1][i] for r in range(4)] == list(ref), (kind, nbytes, starts)
     for r in range(4):
         assert res[r][2].get("device_loop") and res[r][2]["exchanges"] >= res[r][2]["epochs"] > 0
