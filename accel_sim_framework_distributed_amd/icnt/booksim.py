@@ -17,6 +17,15 @@ per injection rate (flits per node per cycle) and optionally a JSON curve.
 grid, and ``--engine gpu`` sends that grid as one batch to the MI355X, one
 wavefront per point (``cpu-par`` runs the same lane-parallel router pass on
 the host; all engines give the same numbers, the default is ``cpu``).
+
+``--request-reply`` runs the traffic the two subnets of a GPU's network
+carry: reads and writes on the request subnet, and for each one, generated at
+its destination when it arrives, a reply of the other size on the reply
+subnet (``read_request_size`` .. ``write_reply_size`` and ``write_fraction``
+from the ``.icnt`` file, Booksim's names; ``--mem-nodes M`` makes the last M
+nodes the memory partitions every request goes to).  ``--replay FILE`` runs a
+packet list of the user's (an ``.npz`` with ``src``, ``dst``, ``flits``,
+``tinj``), for example one dumped from a cycle simulation.
 """
 from __future__ import annotations
 
@@ -59,6 +68,96 @@ def sweep(icnt_text: str, rates: List[float], engine: str = "cpu", traffic="unif
     return out
 
 
+RR_SIZES = ("read_request_size", "read_reply_size", "write_request_size", "write_reply_size")
+
+
+def replay(icnt_text: str, src, dst, flits, tinj, engine: str = "cpu", cycles: int = 0, warmup: int = 0,
+           arrivals: bool = False, mem_budget_mb: int = 0) -> Dict[str, float]:
+    """One packet list through the network (one subnet): packet i goes from
+    ``src[i]`` to ``dst[i]`` with ``flits[i]`` flits, created at cycle
+    ``tinj[i]``; any order.  The summary's window is [warmup, cycles),
+    ``cycles=0``: the last injection + 1."""
+    mod = _native.load(prefer_torch_runtime=engine == "gpu")
+    return dict(mod.icnt_replay_batch(icnt_text, [(src, dst, flits, tinj)], engine=engine, arrivals=arrivals,
+                                      mem_budget_mb=mem_budget_mb, cycles=cycles, warmup=warmup)[0])
+
+
+def request_reply_sweep(icnt_text: str, rates: List[float], engine: str = "cpu", traffic="uniform",
+                        cycles: int = 5000, warmup: int = 1000, seed: int = 1, seeds: Optional[List[int]] = None,
+                        write_fraction: Optional[float] = None, reply_delay: int = 0, mem_nodes: int = 0,
+                        read_request_size: Optional[int] = None, read_reply_size: Optional[int] = None,
+                        write_request_size: Optional[int] = None, write_reply_size: Optional[int] = None,
+                        mem_budget_mb: int = 0, arrivals: bool = False) -> List[Dict]:
+    """The grid traffic x rate x seed of request-reply points as ONE batch
+    through `engine`, like :func:`sweep`.  Reads and writes travel on the
+    request subnet; each one's arrival creates, `reply_delay` cycles later, a
+    reply at its destination, and the replies enter the reply subnet -- a
+    second, independent network of the same file -- in (time, request) order.
+    Unlike Booksim's single-queue ``_IssuePacket``, a pending reply does not
+    hold back its node's requests.  `rate` is flits per node per cycle over
+    both subnets.  The four packet sizes (flits) and `write_fraction` come
+    from the ``.icnt`` keys of the same names when the file has them and the
+    argument is None (else 1 flit and 0.5).  ``mem_nodes=M``: nodes 0..N-M-1
+    issue, to the uniformly drawn nodes N-M..N-1."""
+    mod = _native.load(prefer_torch_runtime=engine == "gpu")
+    kv = mod.parse_booksim_config(icnt_text)
+    given = dict(zip(RR_SIZES, (read_request_size, read_reply_size, write_request_size, write_reply_size)))
+    common = {k: int(v if v is not None else float(kv.get(k, 1))) for k, v in given.items()}
+    common["write_fraction"] = float(write_fraction if write_fraction is not None else kv.get("write_fraction", 0.5))
+    common.update(reply_delay=int(reply_delay), mem_nodes=int(mem_nodes), cycles=int(cycles), warmup=int(warmup))
+    traffics = [traffic] if isinstance(traffic, str) else list(traffic)
+    seed_list = [seed] if seeds is None else list(seeds)
+    multi = len(traffics) > 1 or len(seed_list) > 1
+    grid = [(t, r, s) for t in traffics for r in rates for s in seed_list]
+    res = mod.icnt_request_reply_batch(icnt_text, [dict(common, traffic=t, rate=r, seed=s) for t, r, s in grid],
+                                       engine=engine, arrivals=arrivals, mem_budget_mb=mem_budget_mb)
+    out = []
+    for (t, r, s), d in zip(grid, res):
+        d = dict(d)
+        d["rate"] = r
+        if multi:
+            d["traffic"] = t
+            d["seed"] = s
+        out.append(d)
+    return out
+
+
+def _mean_rr(points: List[Dict], reply_delay: int) -> Dict[str, float]:
+    """The printed figures of one request-reply rate, averaged over its seeds."""
+    n = len(points)
+    m = {"rate": points[0]["rate"]}
+    for side in ("request", "reply"):
+        for k in ("avg_latency", "zero_load_latency", "accepted", "offered"):
+            m[f"{side}_{k}"] = sum(p[side][k] for p in points) / n
+        m[f"{side}_max_latency"] = max(p[side]["max_latency"] for p in points)
+    m["round_trip_latency"] = sum(p["round_trip_latency"] for p in points) / n
+    m["max_round_trip_latency"] = max(p["max_round_trip_latency"] for p in points)
+    m["round_trip_zero_load"] = m["request_zero_load_latency"] + m["reply_zero_load_latency"] + reply_delay
+    for k in ("reads", "writes", "deadlocked"):
+        m[k] = sum(p[k] for p in points)
+    m["measured_packets"] = sum(p["request"]["measured_packets"] for p in points)
+    return m
+
+
+def saturation_round_trip(means: List[Dict[str, float]], factor: float = 3.0) -> float:
+    """Highest offered rate whose round trip stays within `factor` x its zero load."""
+    ok = [c["rate"] for c in means
+          if c["measured_packets"] and c["round_trip_latency"] <= factor * c["round_trip_zero_load"]]
+    return max(ok) if ok else 0.0
+
+
+def _print_open_loop(c: Dict) -> None:
+    print(f"Overall average latency = {c['avg_latency']:.2f} (zero load {c['zero_load_latency']:.2f}, "
+          f"max {c['max_latency']:.0f})")
+    print(f"Overall average accepted rate = {c['accepted']:.4f} (offered {c['offered']:.4f}; "
+          f"drain rate {c['drain_throughput']:.4f})")
+    e = c["energy_pj"]
+    print(f"Network power = {c['power_w']:.3f} W (energy pJ: buffer {e['buffer']:.3g}, crossbar {e['crossbar']:.3g}, "
+          f"link {e['link']:.3g}, allocator {e['allocator']:.3g}, leakage {e['leakage']:.3g})")
+    print(f"Packets = {c['measured_packets']} measured of {c['packets']}"
+          + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
+
+
 def _mean(points: List[Dict[str, float]]) -> Dict[str, float]:
     """The printed figures of one rate, averaged over its seeds (max latency:
     the largest; packet counts: summed)."""
@@ -81,6 +180,39 @@ def saturation(curve: List[Dict[str, float]], factor: float = 3.0) -> float:
     return max(ok) if ok else 0.0
 
 
+def _main_request_reply(a, text: str) -> int:
+    traffics = [t for t in a.traffic.split(",") if t]
+    seeds = list(range(1, a.seeds + 1)) if a.seeds > 0 else None
+    sizes = dict(zip(RR_SIZES, (int(x) for x in a.sizes.split(",")))) if a.sizes else {}
+    rates = [float(x) for x in a.rates.split(",") if x]
+    curve = request_reply_sweep(text, rates, engine=a.engine, traffic=traffics if len(traffics) > 1 else a.traffic,
+                                cycles=a.cycles, warmup=a.warmup, seed=a.seed, seeds=seeds,
+                                write_fraction=a.write_fraction, reply_delay=a.reply_delay, mem_nodes=a.mem_nodes,
+                                mem_budget_mb=a.mem_budget_mb, **sizes)
+    per = len(seeds) if seeds else 1
+    nrate = len(rates)
+    for ti, traffic in enumerate(traffics):
+        means = [_mean_rr(curve[(ti * nrate + ri) * per:(ti * nrate + ri + 1) * per], a.reply_delay)
+                 for ri in range(nrate)]
+        for c in means:
+            print(f"====== Traffic {traffic}, request-reply, injection rate {c['rate']:.3f} ======")
+            for side, name in (("request", "Request"), ("reply", "Reply")):
+                print(f"{name} average latency = {c[side + '_avg_latency']:.2f} "
+                      f"(zero load {c[side + '_zero_load_latency']:.2f}, max {c[side + '_max_latency']:.0f})")
+            print(f"Round-trip average latency = {c['round_trip_latency']:.2f} "
+                  f"(zero load {c['round_trip_zero_load']:.2f}, max {c['max_round_trip_latency']:.0f})")
+            print(f"Accepted rate: request {c['request_accepted']:.4f} (offered {c['request_offered']:.4f}), "
+                  f"reply {c['reply_accepted']:.4f} (offered {c['reply_offered']:.4f})")
+            print(f"Packets = {c['reads']} reads, {c['writes']} writes"
+                  + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
+        print(f"Saturation (round trip <= 3x zero load): {saturation_round_trip(means):.3f} flits/node/cycle")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"config": a.config, "traffic": a.traffic, "request_reply": True, "reply_delay": a.reply_delay,
+                       "mem_nodes": a.mem_nodes, "curve": curve}, f, indent=1)
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("config", help="Booksim .icnt file")
@@ -89,8 +221,8 @@ def main(argv=None) -> int:
     ap.add_argument("--rates", default="0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.8,1.0",
                     help="offered load, flits per node per cycle (comma list)")
     ap.add_argument("--packet-flits", type=int, default=1)
-    ap.add_argument("--cycles", type=int, default=5000)
-    ap.add_argument("--warmup", type=int, default=1000)
+    ap.add_argument("--cycles", type=int, default=None, help="default 5000 (--replay: the last injection + 1)")
+    ap.add_argument("--warmup", type=int, default=None, help="default 1000 (--replay: 0)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--seeds", type=int, default=0,
                     help="run seeds 1..N and print their average per rate (the JSON keeps every point)")
@@ -99,9 +231,34 @@ def main(argv=None) -> int:
                          "gpu: one wavefront per point, the whole grid in one batch")
     ap.add_argument("--mem-budget-mb", type=int, default=0,
                     help="gpu: device memory of one launch (default: half the free device memory)")
+    ap.add_argument("--request-reply", action="store_true",
+                    help="reads and writes on the request subnet, their replies on the reply subnet (sizes and "
+                         "write_fraction from the .icnt file's Booksim keys)")
+    ap.add_argument("--write-fraction", type=float, default=None, help="request-reply: share of writes")
+    ap.add_argument("--reply-delay", type=int, default=0, help="request-reply: the destination's service time, cycles")
+    ap.add_argument("--mem-nodes", type=int, default=0,
+                    help="request-reply: the last M nodes are memory partitions, the others issue to them")
+    ap.add_argument("--sizes", default=None,
+                    help="request-reply: read request, read reply, write request, write reply flits (comma list)")
+    ap.add_argument("--replay", metavar="FILE", help="run the packet list of an .npz (src, dst, flits, tinj)")
     ap.add_argument("--json", help="write the latency / throughput curve here")
     a = ap.parse_args(argv)
     text = open(a.config).read()
+    if a.replay:
+        import numpy as np
+        with np.load(a.replay) as z:
+            c = replay(text, z["src"], z["dst"], z["flits"], z["tinj"], engine=a.engine, cycles=a.cycles or 0,
+                       warmup=a.warmup or 0, mem_budget_mb=a.mem_budget_mb)
+        print(f"====== Replay of {a.replay} ======")
+        _print_open_loop(c)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump({"config": a.config, "replay": a.replay, "result": c}, f, indent=1)
+        return 0
+    a.cycles = 5000 if a.cycles is None else a.cycles
+    a.warmup = 1000 if a.warmup is None else a.warmup
+    if a.request_reply:
+        return _main_request_reply(a, text)
     traffics = [t for t in a.traffic.split(",") if t]
     seeds = list(range(1, a.seeds + 1)) if a.seeds > 0 else None
     curve = sweep(text, [float(x) for x in a.rates.split(",") if x], engine=a.engine,
@@ -116,15 +273,7 @@ def main(argv=None) -> int:
             means.append(_mean(curve[lo:lo + per]))
         for c in means:
             print(f"====== Traffic {traffic}, injection rate {c['rate']:.3f} ======")
-            print(f"Overall average latency = {c['avg_latency']:.2f} (zero load {c['zero_load_latency']:.2f}, "
-                  f"max {c['max_latency']:.0f})")
-            print(f"Overall average accepted rate = {c['accepted']:.4f} (offered {c['offered']:.4f}; "
-                  f"drain rate {c['drain_throughput']:.4f})")
-            e = c["energy_pj"]
-            print(f"Network power = {c['power_w']:.3f} W (energy pJ: buffer {e['buffer']:.3g}, crossbar {e['crossbar']:.3g}, "
-                  f"link {e['link']:.3g}, allocator {e['allocator']:.3g}, leakage {e['leakage']:.3g})")
-            print(f"Packets = {c['measured_packets']} measured of {c['packets']}"
-                  + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
+            _print_open_loop(c)
         print(f"Saturation (latency <= 3x zero load): {saturation(means):.3f} flits/node/cycle")
     if a.json:
         with open(a.json, "w") as f:

@@ -175,6 +175,34 @@ static py::dict open_loop_dict(const OpenLoopResult& r) {
   return d;
 }
 
+// request-reply points from their dicts (a missing field keeps its default)
+static std::vector<RequestReplyParams> rr_points_from(const std::vector<py::dict>& points) {
+  std::vector<RequestReplyParams> ps;
+  for (const py::dict& d : points) {
+    RequestReplyParams p;
+    for (const auto& kv : d) {
+      const std::string k = py::cast<std::string>(kv.first);
+      const py::handle v = kv.second;
+      if (k == "traffic") p.traffic = py::cast<std::string>(v);
+      else if (k == "rate") p.rate = py::cast<double>(v);
+      else if (k == "cycles") p.cycles = py::cast<uint64_t>(v);
+      else if (k == "warmup") p.warmup = py::cast<uint64_t>(v);
+      else if (k == "seed") p.seed = py::cast<uint64_t>(v);
+      else if (k == "write_fraction") p.write_fraction = py::cast<double>(v);
+      else if (k == "read_request_size") p.read_request_size = py::cast<uint32_t>(v);
+      else if (k == "read_reply_size") p.read_reply_size = py::cast<uint32_t>(v);
+      else if (k == "write_request_size") p.write_request_size = py::cast<uint32_t>(v);
+      else if (k == "write_reply_size") p.write_reply_size = py::cast<uint32_t>(v);
+      else if (k == "reply_delay") p.reply_delay = py::cast<uint64_t>(v);
+      else if (k == "mem_nodes") p.mem_nodes = py::cast<uint32_t>(v);
+      else throw std::invalid_argument("icnt_request_reply_batch: point " + std::to_string(ps.size()) +
+                                       ": unknown field '" + k + "'");
+    }
+    ps.push_back(p);
+  }
+  return ps;
+}
+
 PYBIND11_MODULE(_asim, m) {
   m.doc() = "MI355X-native trace-driven GPU simulator (native core)";
   m.attr("sizeof_SMState") = sizeof(SMState);
@@ -344,6 +372,143 @@ PYBIND11_MODULE(_asim, m) {
     return d;
   }, "how the last gpu batch of this process was packed into launches");
   m.def("icnt_sweep_kernel_info", &icnt_sweep_kernel_info, "registers, LDS and scratch of the sweep kernel");
+  m.def(
+      "icnt_replay_batch",
+      [](const std::string& icnt_text, const py::list& lists, const std::string& engine, bool arrivals,
+         uint64_t mem_budget_mb, uint64_t step_cap, bool lds, uint64_t cycles, uint64_t warmup) {
+        typedef py::array_t<uint32_t, py::array::c_style | py::array::forcecast> A32;
+        typedef py::array_t<uint64_t, py::array::c_style | py::array::forcecast> A64;
+        std::vector<ReplayList> ls;
+        for (const py::handle& h : lists) {
+          const py::tuple t = py::cast<py::tuple>(h);
+          if (t.size() != 4)
+            throw std::invalid_argument("icnt_replay_batch: list " + std::to_string(ls.size()) +
+                                        ": expected (src, dst, flits, tinj)");
+          const A32 s = A32::ensure(t[0]), d = A32::ensure(t[1]), f = A32::ensure(t[2]);
+          const A64 ti = A64::ensure(t[3]);
+          if (!s || !d || !f || !ti || s.ndim() != 1 || d.ndim() != 1 || f.ndim() != 1 || ti.ndim() != 1)
+            throw std::invalid_argument("icnt_replay_batch: list " + std::to_string(ls.size()) +
+                                        ": src, dst, flits and tinj must be one-dimensional integer arrays");
+          if ((uint64_t)s.size() > kReplayMaxPackets)
+            throw std::invalid_argument("icnt_replay_batch: list " + std::to_string(ls.size()) +
+                                        ": too many packets for one pass");
+          ReplayList l;
+          l.src.assign(s.data(), s.data() + s.size());
+          l.dst.assign(d.data(), d.data() + d.size());
+          l.flits.assign(f.data(), f.data() + f.size());
+          l.tinj.assign(ti.data(), ti.data() + ti.size());
+          ls.push_back(std::move(l));
+        }
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<OpenLoopResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_replay_batch(icnt_text, ls, engine, o, cycles, warmup);
+        }
+        py::list out;
+        for (const OpenLoopResult& r : rs) {
+          py::dict d = open_loop_dict(r);
+          if (arrivals) {
+            d["arrivals"] = py::array_t<uint64_t>((py::ssize_t)r.arrivals.size(), r.arrivals.data());
+            d["state"] = py::array_t<uint64_t>((py::ssize_t)r.state.size(), r.state.data());
+          }
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("icnt_text"), py::arg("lists"), py::arg("engine") = "cpu", py::arg("arrivals") = false,
+      py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true, py::kw_only(),
+      py::arg("cycles") = 0, py::arg("warmup") = 0,
+      "packet lists (src, dst, flits, tinj: uint32 x 3 and uint64 arrays of one length, any order) through one "
+      "engine, one subnet, every packet with its own flit count; the summary's window is [warmup, cycles), "
+      "cycles=0: the list's last injection + 1.  ValueError names the list and packet of a bad entry");
+  m.def(
+      "icnt_request_reply_batch",
+      [](const std::string& icnt_text, const std::vector<py::dict>& points, const std::string& engine, bool arrivals,
+         uint64_t mem_budget_mb, uint64_t step_cap, bool lds) {
+        const std::vector<RequestReplyParams> ps = rr_points_from(points);
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<RequestReplyResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_request_reply_batch(icnt_text, ps, engine, o);
+        }
+        auto a32 = [](const std::vector<uint32_t>& v) { return py::array_t<uint32_t>((py::ssize_t)v.size(), v.data()); };
+        auto a64 = [](const std::vector<uint64_t>& v) { return py::array_t<uint64_t>((py::ssize_t)v.size(), v.data()); };
+        py::list out;
+        for (const RequestReplyResult& r : rs) {
+          py::dict d;
+          d["request"] = open_loop_dict(r.request);
+          d["reply"] = open_loop_dict(r.reply);
+          d["reads"] = r.reads;
+          d["writes"] = r.writes;
+          d["round_trip_latency"] = r.round_trip_latency;
+          d["max_round_trip_latency"] = r.max_round_trip_latency;
+          d["deadlocked"] = r.deadlocked;
+          if (arrivals) {
+            d["request_src"] = a32(r.request_src);
+            d["request_dst"] = a32(r.request_dst);
+            d["request_flits"] = a32(r.request_flits);
+            d["request_tinj"] = a64(r.request_tinj);
+            d["request_arrivals"] = a64(r.request.arrivals);
+            d["request_state"] = a64(r.request.state);
+            d["reply_of"] = a32(r.reply_of);
+            d["reply_src"] = a32(r.reply_src);
+            d["reply_dst"] = a32(r.reply_dst);
+            d["reply_flits"] = a32(r.reply_flits);
+            d["reply_tinj"] = a64(r.reply_tinj);
+            d["reply_arrivals"] = a64(r.reply.arrivals);
+            d["reply_state"] = a64(r.reply.state);
+          }
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("icnt_text"), py::arg("points"), py::arg("engine") = "cpu", py::arg("arrivals") = false,
+      py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true,
+      "request-reply points over two subnets.  A point is a dict: traffic, rate, cycles, warmup, seed, "
+      "write_fraction (0.5), read_request_size / read_reply_size / write_request_size / write_reply_size (1 flit "
+      "each), reply_delay (0), mem_nodes (0).  Reads and writes travel on the request subnet; a request's delivery "
+      "creates, reply_delay cycles later, its reply at the destination, and the replies enter the reply subnet in "
+      "(time, request) order.  The reply subnet is a second, independent network of the same .icnt (the "
+      "two-subnet arrangement of gputrafficmanager.cpp); unlike Booksim's single-queue _IssuePacket, a pending "
+      "reply does not hold back its node's requests.  engine gpu runs both passes and the reply ordering of a "
+      "point in one workgroup of one launch");
+  m.def(
+      "icnt_request_reply_schedule",
+      [](const std::string& icnt_text, const std::vector<py::dict>& points) {
+        const std::vector<RequestReplyParams> ps = rr_points_from(points);
+        std::vector<RequestReplySchedule> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_request_reply_schedule(icnt_text, ps);
+        }
+        auto a32 = [](const std::vector<uint32_t>& v) { return py::array_t<uint32_t>((py::ssize_t)v.size(), v.data()); };
+        py::list out;
+        for (const RequestReplySchedule& r : rs) {
+          py::dict d;
+          d["src"] = a32(r.src);
+          d["dst"] = a32(r.dst);
+          d["flits"] = a32(r.flits);
+          d["tinj"] = py::array_t<uint64_t>((py::ssize_t)r.tinj.size(), r.tinj.data());
+          d["kind"] = a32(r.kind);
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("icnt_text"), py::arg("points"),
+      "the request subnet's packet list of every request-reply point (src, dst, flits, tinj; kind: 1 a write), "
+      "as icnt_request_reply_batch simulates it; the first four replay as they are (icnt_replay_batch)");
+  m.def("icnt_rr_kernel_info", &icnt_rr_kernel_info,
+        "registers, LDS and scratch of the replay / request-reply kernel");
   m.def(
       "arch_energy",
       [](const std::vector<std::string>& args, double node_nm, double vdd, double dram_pj_per_bit,

@@ -7,6 +7,13 @@
 // schedule is known up front.  Latency is creation to tail ejection (source
 // queueing included), accepted throughput the flits ejected during the
 // measurement window [warmup, cycles) per node and cycle.
+//
+// Two more kinds of run share the pass and the summary (second half of this
+// file): packet lists the caller brings, every packet with its own flit count
+// (icnt_replay_batch), and request-reply points over two subnets, where a
+// request's arrival creates its reply at the destination (reference
+// trafficmanager.cpp _IssuePacket / _GeneratePacket; icnt_request_reply_batch,
+// model/icnt_reqreply.h).
 #include "icnt_bench.h"
 
 #include <algorithm>
@@ -22,6 +29,7 @@
 #include "../engine/engine.h"
 #include "../engine/icnt_sweep.h"
 #include "../model/icnt_router.h"
+#include "../model/icnt_reqreply.h"
 #include "../model/icnt_router_par.h"
 
 namespace asim {
@@ -206,7 +214,7 @@ RtWork load_point(const OpenLoopNet& net, const OpenLoopPoint& pt, std::vector<u
   for (uint32_t i = 0; i < pt.np; ++i) {
     w.src[i] = pt.src[i];
     w.dst[i] = pt.dst[i];
-    w.nfl[i] = pt.pf;
+    w.nfl[i] = pt.flits(i);
     w.tinj[i] = pt.tinj[i];
   }
   return w;
@@ -229,10 +237,28 @@ OpenLoopRaw simulate_host(const OpenLoopNet& net, const OpenLoopPoint& pt, bool 
 
 OpenLoopBatchStats g_last;  // of the last batch call (one caller at a time)
 
-void check_status(const OpenLoopRaw& raw, size_t index) {
+void check_status(const OpenLoopRaw& raw, size_t index, const char* who = "icnt_open_loop_batch: point ") {
   if (raw.status != RT_STATUS_OK)
-    throw std::runtime_error("icnt_open_loop_batch: point " + std::to_string(index) +
-                             ": the router pass exceeded its step cap (loop guard)");
+    throw std::runtime_error(who + std::to_string(index) + ": the router pass exceeded its step cap (loop guard)");
+}
+
+void check_engine(const std::string& who, const std::string& engine) {
+  if (engine != "cpu" && engine != "cpu-par" && engine != "gpu")
+    throw std::invalid_argument(who + ": engine must be cpu, cpu-par or gpu, not '" + engine + "'");
+  if (engine == "gpu" && !gpu_engine_available())
+    throw std::runtime_error(who + ": engine 'gpu' needs a HIP device, and none is usable");
+}
+
+// the dimensions of a pass of np packets of at most max_flits flits
+RtDims list_dims(const OpenLoopNet& net, uint32_t np, uint32_t max_flits) {
+  RtDims d = rt_dims(net.c, np ? np : 1, max_flits ? max_flits : 1);
+  if (net.anynet) {
+    d.N = net.N;
+    d.L = net.an_L;
+    d.U = d.N + d.L;
+    d.H = net.an_H;
+  }
+  return d;
 }
 
 }  // namespace
@@ -304,14 +330,7 @@ OpenLoopPoint icnt_open_loop_prepare(const OpenLoopNet& net, const OpenLoopParam
   if (np64 > 50'000'000ull) throw std::invalid_argument("too many packets for one pass");
   const uint32_t np = (uint32_t)np64;
   pt.np = np;
-  RtDims d = rt_dims(c, np ? np : 1, pf);
-  if (anynet) {
-    d.N = N;
-    d.L = net.an_L;
-    d.U = d.N + d.L;
-    d.H = net.an_H;
-  }
-  pt.d = d;
+  pt.d = list_dims(net, np, pf);
   return pt;
 }
 
@@ -320,7 +339,7 @@ OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPo
   const auto& kv = net.kv;
   const OpenLoopParams& prm = pt.prm;
   const bool anynet = net.anynet;
-  const uint32_t N = net.N, np = pt.np, pf = pt.pf;
+  const uint32_t N = net.N, np = pt.np;
   const RtDims& d = pt.d;
   const std::vector<uint32_t>&src = pt.src, &dst = pt.dst;
   const std::vector<uint64_t>& tinj = pt.tinj;
@@ -331,10 +350,12 @@ OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPo
   res.deadlocked = raw.deadlocked;
   for (int i = 0; i < RT_ACT_COUNT; ++i) res.activity[i] = act[i];
   double lat = 0, zero = 0;
-  uint64_t meas = 0, ejected = 0, last = 0;
+  uint64_t meas = 0, meas_flits = 0, total = 0, ejected = 0, last = 0;  // (flit sums: exact in a double)
   for (uint32_t i = 0; i < np; ++i) {
     const uint64_t a = raw.tarr[i];
     last = std::max(last, a);
+    const uint32_t pf = pt.flits(i);
+    total += pf;
     if (a >= prm.warmup && a < prm.cycles) ejected += pf;
     if (tinj[i] >= prm.warmup) {
       lat += (double)(a - tinj[i]);
@@ -348,18 +369,19 @@ OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPo
         zero += (double)rt_uncontended(c, icnt_routers(c, src[i], dst[i]), pf);
       }
       ++meas;
+      meas_flits += pf;
       res.max_latency = std::max<double>(res.max_latency, (double)(a - tinj[i]));
     }
   }
   const double window = (double)(prm.cycles - prm.warmup) * N;
-  res.offered = (double)meas * pf / window;
+  res.offered = (double)meas_flits / window;
   res.accepted = (double)ejected / window;
   res.avg_latency = meas ? lat / meas : 0;
   res.zero_load_latency = meas ? zero / meas : 0;
   res.measured_packets = meas;
   // above saturation the window sees the network before its queues settle;
   // the drain rate is the bottleneck's (open loop, every packet delivered)
-  res.drain_throughput = np && last ? (double)np * pf / ((double)N * (double)(last + 1)) : 0;
+  res.drain_throughput = np && last ? (double)total / ((double)N * (double)(last + 1)) : 0;
   // network energy from the activity (Booksim power_module.cpp's terms:
   // input buffers, crossbar, channels, allocators, buffer leakage); the
   // per-event energies are .icnt keys with ~22 nm Orion-class defaults
@@ -392,10 +414,7 @@ OpenLoopResult icnt_open_loop(const std::string& icnt_text, const OpenLoopParams
 std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
                                                  const std::vector<OpenLoopParams>& points,
                                                  const std::string& engine, const OpenLoopBatchOpts& opts) {
-  if (engine != "cpu" && engine != "cpu-par" && engine != "gpu")
-    throw std::invalid_argument("icnt_open_loop_batch: engine must be cpu, cpu-par or gpu, not '" + engine + "'");
-  if (engine == "gpu" && !gpu_engine_available())
-    throw std::runtime_error("icnt_open_loop_batch: engine 'gpu' needs a HIP device, and none is usable");
+  check_engine("icnt_open_loop_batch", engine);
   const OpenLoopNet net = icnt_open_loop_net(icnt_text);
   std::vector<OpenLoopResult> out;
   out.reserve(points.size());
@@ -449,5 +468,320 @@ std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
   return out;
 }
 
-}  // namespace asim
+// ---- packet-list replay and request-reply points ----
 
+namespace {
+
+// gpu: the items are prepared one after the other and packed into chunks under
+// the memory budget; a full chunk is launched, finished and dropped.
+// prep(i): item i; unit(item): its RrUnit; done(item, raw): its result.
+template <class Item, class Prep, class Unit, class Done>
+void rr_gpu_batch(const std::string& who, const OpenLoopNet& net, size_t n, const OpenLoopBatchOpts& opts, Prep prep,
+                  Unit unit, Done done) {
+  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb);
+  g_last.budget_bytes = budget;
+  std::vector<Item> chunk;
+  uint64_t used = 0;
+  auto flush = [&] {
+    if (chunk.empty()) return;
+    std::vector<RrUnit> units;
+    for (const Item& it : chunk) units.push_back(unit(it));
+    std::vector<RrRaw> raws;
+    if (icnt_rr_run_chunk(net, units, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
+    ++g_last.chunks;
+    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
+    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
+    for (size_t i = 0; i < chunk.size(); ++i) done(chunk[i], raws[i]);
+    chunk.clear();
+    used = 0;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    Item it = prep(i);
+    const uint64_t need = icnt_rr_unit_bytes(unit(it));
+    if (need > budget)
+      throw std::invalid_argument(who + " " + std::to_string(i) + " needs " +
+                                  std::to_string((need + (1u << 20) - 1) >> 20) + " MB, the memory budget is " +
+                                  std::to_string(budget >> 20) + " MB");
+    if (used + need > budget) flush();
+    used += need;
+    chunk.push_back(std::move(it));
+  }
+  flush();
+}
+
+// a checked packet list as a point of the pass; `index` names it in errors
+OpenLoopPoint replay_prepare(const OpenLoopNet& net, const ReplayList& l, size_t index, uint64_t cycles,
+                             uint64_t warmup) {
+  const std::string who = "icnt_replay_batch: list " + std::to_string(index);
+  const size_t n = l.src.size();
+  if (l.dst.size() != n || l.flits.size() != n || l.tinj.size() != n)
+    throw std::invalid_argument(who + ": src, dst, flits and tinj differ in length");
+  if (n > kReplayMaxPackets) throw std::invalid_argument(who + ": too many packets for one pass");
+  const uint32_t max_fl = rt_flits(net.c, kRtMaxPktBytes);
+  uint32_t top = 1;
+  uint64_t last = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const std::string pk = who + ", packet " + std::to_string(i);
+    if (l.src[i] >= net.N || l.dst[i] >= net.N)
+      throw std::invalid_argument(pk + ": node out of range (the network has " + std::to_string(net.N) + ")");
+    if (l.src[i] == l.dst[i]) throw std::invalid_argument(pk + ": source and destination are the same node");
+    if (!l.flits[i] || l.flits[i] > max_fl)
+      throw std::invalid_argument(pk + ": flits must be 1.." + std::to_string(max_fl));
+    top = std::max(top, l.flits[i]);
+    last = std::max(last, l.tinj[i]);
+  }
+  OpenLoopPoint pt;
+  pt.prm.traffic = "replay";
+  pt.prm.rate = 0;
+  pt.prm.cycles = cycles ? cycles : last + 1;
+  pt.prm.warmup = warmup;
+  if (pt.prm.warmup >= pt.prm.cycles) throw std::invalid_argument(who + ": warmup must be shorter than the run");
+  pt.np = (uint32_t)n;
+  pt.src = l.src;
+  pt.dst = l.dst;
+  pt.nfl = l.flits;
+  pt.tinj = l.tinj;
+  pt.d = list_dims(net, pt.np, top);  // nf = np * the largest packet
+  return pt;
+}
+
+// a request-reply point: the request schedule with its kinds, and the reply
+// subnet's dimensions
+struct RrPoint {
+  RequestReplyParams prm;
+  OpenLoopPoint req;
+  std::vector<uint32_t> kind;  // per request: 1 a write
+  RtDims d_rep{};
+  uint64_t reads = 0, writes = 0;
+};
+
+RrPoint rr_prepare(const OpenLoopNet& net, const RequestReplyParams& prm, size_t index) {
+  const std::string who = "icnt_request_reply_batch: point " + std::to_string(index);
+  const SimCfg& c = net.c;
+  const uint32_t N = net.N, M = prm.mem_nodes;
+  if (prm.rate < 0 || prm.rate > 1) throw std::invalid_argument(who + ": rate must be 0..1 flits per node per cycle");
+  if (prm.warmup >= prm.cycles) throw std::invalid_argument(who + ": warmup must be shorter than the run");
+  if (!(prm.write_fraction >= 0 && prm.write_fraction <= 1))
+    throw std::invalid_argument(who + ": write_fraction must be 0..1");
+  const uint32_t max_fl = rt_flits(c, kRtMaxPktBytes);
+  for (uint32_t sz : {prm.read_request_size, prm.read_reply_size, prm.write_request_size, prm.write_reply_size})
+    if (!sz || sz > max_fl) throw std::invalid_argument(who + ": packet sizes must be 1.." + std::to_string(max_fl) + " flits");
+  if (M >= N) throw std::invalid_argument(who + ": mem_nodes must leave a node to issue");
+  if (M && prm.traffic != "uniform") throw std::invalid_argument(who + ": mem_nodes needs uniform traffic");
+  RrPoint pt;
+  pt.prm = prm;
+  OpenLoopPoint& q = pt.req;
+  q.prm.traffic = prm.traffic;
+  q.prm.rate = prm.rate;
+  q.prm.cycles = prm.cycles;
+  q.prm.warmup = prm.warmup;
+  q.prm.seed = prm.seed;
+  // the request schedule: the generator and loop of icnt_open_loop_prepare,
+  // with the packet probability over the average packet of both subnets
+  // (reference trafficmanager.cpp:197-200) and a kind draw per kept packet
+  const uint32_t avg = std::max<uint32_t>(
+      1, (prm.read_request_size + prm.read_reply_size + prm.write_request_size + prm.write_reply_size) / 2);
+  const double p_pkt = prm.rate / avg;
+  const uint32_t issuers = N - M;
+  Rng r{prm.seed * 0x2545f4914f6cdd1dull + 1};
+  for (uint64_t t = 0; t < prm.cycles; ++t)
+    for (uint32_t s = 0; s < issuers; ++s)
+      if (r.uniform() < p_pkt) {
+        const uint32_t d = M ? N - M + (uint32_t)(r.next() % M)
+                             : destination(prm.traffic, s, N, net.anynet ? N : c.topo_k, net.anynet ? 1u : c.topo_n, r);
+        if (d == s) continue;  // a fixed point of a permutation sends nothing
+        const uint32_t wr = r.uniform() < prm.write_fraction ? 1u : 0u;
+        q.src.push_back(s);
+        q.dst.push_back(d);
+        q.tinj.push_back(t);
+        q.nfl.push_back(wr ? prm.write_request_size : prm.read_request_size);
+        pt.kind.push_back(wr);
+        ++(wr ? pt.writes : pt.reads);
+      }
+  if (q.src.size() > kReplayMaxPackets) throw std::invalid_argument(who + ": too many packets for one pass");
+  q.np = (uint32_t)q.src.size();
+  q.d = list_dims(net, q.np, std::max(prm.read_request_size, prm.write_request_size));
+  pt.d_rep = list_dims(net, q.np, std::max(prm.read_reply_size, prm.write_reply_size));
+  return pt;
+}
+
+RrUnit rr_unit(const RrPoint& pt) {
+  RrUnit u;
+  u.req = &pt.req;
+  u.reply = true;
+  u.d_rep = pt.d_rep;
+  u.kind = &pt.kind;
+  u.fl_read = pt.prm.read_reply_size;
+  u.fl_write = pt.prm.write_reply_size;
+  u.delay = pt.prm.reply_delay;
+  return u;
+}
+
+// the reply subnet's point from the schedule in `raw`
+OpenLoopPoint rr_reply_point(const RrPoint& pt, const RrRaw& raw) {
+  OpenLoopPoint p;
+  p.prm = pt.req.prm;
+  p.np = pt.req.np;
+  p.d = pt.d_rep;
+  p.src = raw.rep_src;
+  p.dst = raw.rep_dst;
+  p.nfl = raw.rep_nfl;
+  p.tinj = raw.rep_tinj;
+  return p;
+}
+
+// both subnets of a point on the host.  cpu: the reply order by a plain
+// std::stable_sort, the independent form of model/icnt_reqreply.h's rule;
+// cpu-par: rt_reply_build under the sequential lane policy
+RrRaw rr_host(const OpenLoopNet& net, const RrPoint& pt, bool par, uint64_t step_cap, size_t index) {
+  RrRaw raw;
+  const uint32_t np = pt.req.np;
+  raw.req = simulate_host(net, pt.req, par, step_cap);
+  check_status(raw.req, index, "icnt_request_reply_batch: point ");
+  raw.reply_of.assign(np, 0);
+  raw.rep_src.assign(np, 0);
+  raw.rep_dst.assign(np, 0);
+  raw.rep_nfl.assign(np, 0);
+  raw.rep_tinj.assign(np, 0);
+  const RequestReplyParams& prm = pt.prm;
+  if (par) {
+    const RtReplyIn rq{pt.req.src.data(), pt.req.dst.data(), pt.kind.data(), raw.req.tarr.data()};
+    const RtReplyOut rp{raw.rep_src.data(), raw.rep_dst.data(), raw.rep_nfl.data(), raw.rep_tinj.data()};
+    std::vector<uint32_t> tmp(np);
+    rt_reply_build<SeqPar>(np, rq, rp, prm.read_reply_size, prm.write_reply_size, prm.reply_delay,
+                           raw.reply_of.data(), tmp.data());
+  } else {
+    for (uint32_t i = 0; i < np; ++i) raw.reply_of[i] = i;
+    std::stable_sort(raw.reply_of.begin(), raw.reply_of.end(),
+                     [&](uint32_t a, uint32_t b) { return raw.req.tarr[a] < raw.req.tarr[b]; });
+    for (uint32_t j = 0; j < np; ++j) {
+      const uint32_t i = raw.reply_of[j];
+      raw.rep_src[j] = pt.req.dst[i];
+      raw.rep_dst[j] = pt.req.src[i];
+      raw.rep_nfl[j] = pt.kind[i] ? prm.write_reply_size : prm.read_reply_size;
+      raw.rep_tinj[j] = raw.req.tarr[i] + prm.reply_delay;
+    }
+  }
+  raw.rep = simulate_host(net, rr_reply_point(pt, raw), par, step_cap);
+  return raw;
+}
+
+RequestReplyResult rr_finish(const OpenLoopNet& net, RrPoint& pt, RrRaw& raw, bool arrivals, size_t index) {
+  check_status(raw.req, index, "icnt_request_reply_batch: point ");
+  check_status(raw.rep, index, "icnt_request_reply_batch: point ");
+  RequestReplyResult res;
+  const OpenLoopPoint rep = rr_reply_point(pt, raw);
+  res.request = icnt_open_loop_summarise(net, pt.req, raw.req);
+  res.reply = icnt_open_loop_summarise(net, rep, raw.rep);
+  res.reads = pt.reads;
+  res.writes = pt.writes;
+  res.deadlocked = raw.req.deadlocked + raw.rep.deadlocked;
+  double sum = 0;
+  uint64_t meas = 0;
+  for (uint32_t j = 0; j < rep.np; ++j) {
+    const uint32_t i = raw.reply_of[j];
+    if (pt.req.tinj[i] < pt.prm.warmup) continue;
+    const double rt = (double)(raw.rep.tarr[j] - pt.req.tinj[i]);
+    sum += rt;
+    ++meas;
+    res.max_round_trip_latency = std::max(res.max_round_trip_latency, rt);
+  }
+  res.round_trip_latency = meas ? sum / meas : 0;
+  if (arrivals) {
+    res.request.arrivals = std::move(raw.req.tarr);
+    res.request.state = std::move(raw.req.state);
+    res.reply.arrivals = std::move(raw.rep.tarr);
+    res.reply.state = std::move(raw.rep.state);
+    res.request_src = std::move(pt.req.src);
+    res.request_dst = std::move(pt.req.dst);
+    res.request_flits = std::move(pt.req.nfl);
+    res.request_tinj = std::move(pt.req.tinj);
+    res.reply_of = std::move(raw.reply_of);
+    res.reply_src = std::move(raw.rep_src);
+    res.reply_dst = std::move(raw.rep_dst);
+    res.reply_flits = std::move(raw.rep_nfl);
+    res.reply_tinj = std::move(raw.rep_tinj);
+  }
+  return res;
+}
+
+}  // namespace
+
+std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, const std::vector<ReplayList>& lists,
+                                              const std::string& engine, const OpenLoopBatchOpts& opts, uint64_t cycles,
+                                              uint64_t warmup) {
+  check_engine("icnt_replay_batch", engine);
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  std::vector<OpenLoopResult> out;
+  out.reserve(lists.size());
+  auto finish = [&](const OpenLoopPoint& pt, OpenLoopRaw& raw) {
+    check_status(raw, out.size(), "icnt_replay_batch: list ");
+    OpenLoopResult r = icnt_open_loop_summarise(net, pt, raw);
+    if (opts.arrivals) {
+      r.arrivals = std::move(raw.tarr);
+      r.state = std::move(raw.state);
+    }
+    out.push_back(std::move(r));
+  };
+  g_last = OpenLoopBatchStats();
+  if (engine != "gpu") {
+    for (size_t i = 0; i < lists.size(); ++i) {
+      const OpenLoopPoint pt = replay_prepare(net, lists[i], i, cycles, warmup);
+      OpenLoopRaw raw = simulate_host(net, pt, engine == "cpu-par", opts.step_cap);
+      finish(pt, raw);
+    }
+    return out;
+  }
+  rr_gpu_batch<OpenLoopPoint>(
+      "icnt_replay_batch: list", net, lists.size(), opts,
+      [&](size_t i) { return replay_prepare(net, lists[i], i, cycles, warmup); },
+      [](const OpenLoopPoint& pt) {
+        RrUnit u;
+        u.req = &pt;
+        return u;
+      },
+      [&](OpenLoopPoint& pt, RrRaw& raw) { finish(pt, raw.req); });
+  return out;
+}
+
+std::vector<RequestReplySchedule> icnt_request_reply_schedule(const std::string& icnt_text,
+                                                              const std::vector<RequestReplyParams>& points) {
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  std::vector<RequestReplySchedule> out;
+  for (size_t i = 0; i < points.size(); ++i) {
+    RrPoint pt = rr_prepare(net, points[i], i);
+    RequestReplySchedule s;
+    s.src = std::move(pt.req.src);
+    s.dst = std::move(pt.req.dst);
+    s.flits = std::move(pt.req.nfl);
+    s.kind = std::move(pt.kind);
+    s.tinj = std::move(pt.req.tinj);
+    out.push_back(std::move(s));
+  }
+  return out;
+}
+
+std::vector<RequestReplyResult> icnt_request_reply_batch(const std::string& icnt_text,
+                                                         const std::vector<RequestReplyParams>& points,
+                                                         const std::string& engine, const OpenLoopBatchOpts& opts) {
+  check_engine("icnt_request_reply_batch", engine);
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  std::vector<RequestReplyResult> out;
+  out.reserve(points.size());
+  g_last = OpenLoopBatchStats();
+  if (engine != "gpu") {
+    for (size_t i = 0; i < points.size(); ++i) {
+      RrPoint pt = rr_prepare(net, points[i], i);
+      RrRaw raw = rr_host(net, pt, engine == "cpu-par", opts.step_cap, i);
+      out.push_back(rr_finish(net, pt, raw, opts.arrivals, i));
+    }
+    return out;
+  }
+  rr_gpu_batch<RrPoint>(
+      "icnt_request_reply_batch: point", net, points.size(), opts,
+      [&](size_t i) { return rr_prepare(net, points[i], i); }, rr_unit,
+      [&](RrPoint& pt, RrRaw& raw) { out.push_back(rr_finish(net, pt, raw, opts.arrivals, out.size())); });
+  return out;
+}
+
+}  // namespace asim

@@ -1,4 +1,5 @@
-// Open-loop synthetic traffic through the router model (icnt_bench.cc).
+// Open-loop synthetic traffic, packet-list replay and request-reply traffic
+// through the router model (icnt_bench.cc).
 #pragma once
 #include <cstdint>
 #include <map>
@@ -60,6 +61,8 @@ struct OpenLoopPoint {
   RtDims d{};
   std::vector<uint32_t> src, dst;
   std::vector<uint64_t> tinj;
+  std::vector<uint32_t> nfl;  // per-packet flits (replay, request-reply); empty: pf for every packet
+  uint32_t flits(uint32_t i) const { return nfl.empty() ? pf : nfl[i]; }
 };
 
 // what a router pass leaves
@@ -97,5 +100,70 @@ std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
                                                  const std::vector<OpenLoopParams>& points,
                                                  const std::string& engine = "cpu",
                                                  const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
+
+// ---- packet-list replay: one subnet, per-packet sizes ----
+
+// a packet list the caller brings (for example one dumped from a cycle
+// simulation): packet i goes from src[i] to dst[i] with flits[i] flits and is
+// created at cycle tinj[i]; any order
+struct ReplayList {
+  std::vector<uint32_t> src, dst, flits;
+  std::vector<uint64_t> tinj;
+};
+constexpr uint64_t kReplayMaxPackets = 50'000'000ull;
+
+// every list through one engine, like icnt_open_loop_batch; the summary's
+// window is [warmup, cycles), cycles 0: the list's last injection + 1.
+// std::invalid_argument, naming the list and the packet: a node out of range,
+// src == dst, flits 0 or above rt_flits(c, kRtMaxPktBytes), arrays of unequal
+// length, more than kReplayMaxPackets packets.
+std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, const std::vector<ReplayList>& lists,
+                                              const std::string& engine = "cpu",
+                                              const OpenLoopBatchOpts& opts = OpenLoopBatchOpts(),
+                                              uint64_t cycles = 0, uint64_t warmup = 0);
+
+// ---- request-reply points: two subnets ----
+
+// Reads and writes travel on the request subnet; each one's delivery creates,
+// `reply_delay` cycles later, a reply of the other size from the destination
+// back to the source on the reply subnet (model/icnt_reqreply.h).  The two
+// subnets are independent networks of the same .icnt file (the arrangement of
+// the reference's gputrafficmanager.cpp); unlike Booksim's single-queue
+// _IssuePacket, a pending reply does not hold back its node's requests.
+struct RequestReplyParams {
+  std::string traffic = "uniform";
+  double rate = 0.1;  // flits per node per cycle over both subnets
+  uint64_t cycles = 2000, warmup = 500;
+  uint64_t seed = 1;
+  double write_fraction = 0.5;
+  uint32_t read_request_size = 1, read_reply_size = 1, write_request_size = 1, write_reply_size = 1;  // flits
+  uint64_t reply_delay = 0;  // the destination's service time, cycles
+  uint32_t mem_nodes = 0;    // M > 0: nodes 0 .. N-M-1 issue, to the uniformly drawn memory nodes N-M .. N-1
+};
+
+struct RequestReplyResult {
+  OpenLoopResult request, reply;
+  uint64_t reads = 0, writes = 0;
+  // request creation to reply tail arrival, over the requests created at or after warmup
+  double round_trip_latency = 0, max_round_trip_latency = 0;
+  uint32_t deadlocked = 0;  // both subnets
+  // on request (opts.arrivals): both schedules; request.arrivals / .state and reply.arrivals / .state hold the rest
+  std::vector<uint32_t> request_src, request_dst, request_flits, reply_of, reply_src, reply_dst, reply_flits;
+  std::vector<uint64_t> request_tinj, reply_tinj;
+};
+
+// the request subnet's schedule of every point (what the batch call simulates):
+// kind[i] is 1 for a write; host work only
+struct RequestReplySchedule {
+  std::vector<uint32_t> src, dst, flits, kind;
+  std::vector<uint64_t> tinj;
+};
+std::vector<RequestReplySchedule> icnt_request_reply_schedule(const std::string& icnt_text,
+                                                              const std::vector<RequestReplyParams>& points);
+
+std::vector<RequestReplyResult> icnt_request_reply_batch(const std::string& icnt_text,
+                                                         const std::vector<RequestReplyParams>& points,
+                                                         const std::string& engine = "cpu",
+                                                         const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
 
 }  // namespace asim

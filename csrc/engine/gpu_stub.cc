@@ -49,4 +49,9 @@ bool icnt_sweep_run_chunk(const OpenLoopNet&, const std::vector<OpenLoopPoint>&,
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_sweep_kernel_info() { return {}; }
+uint64_t icnt_rr_unit_bytes(const RrUnit&) { return 0; }
+bool icnt_rr_run_chunk(const OpenLoopNet&, const std::vector<RrUnit>&, uint64_t, bool, std::vector<RrRaw>&) {
+  throw std::runtime_error("no GPU engine in this build");
+}
+std::map<std::string, uint64_t> icnt_rr_kernel_info() { return {}; }
 }  // namespace asim

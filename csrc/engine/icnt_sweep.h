@@ -2,8 +2,10 @@
 // wavefront per sweep point runs the lane-parallel router pass
 // (model/icnt_router_par.h) on that point's scratch in HBM.  The caller
 // (driver/icnt_bench.cc icnt_open_loop_batch) packs the points into chunks
-// under a memory budget; one chunk is one launch.  Host-only builds link the
-// stub in gpu_stub.cc.
+// under a memory budget; one chunk is one launch.  A second kernel
+// (icnt_rr_sweep.hip) takes packet lists with per-packet sizes and
+// request-reply points, both subnets of a point in one wavefront.  Host-only
+// builds link the stub in gpu_stub.cc.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -36,5 +38,36 @@ bool icnt_sweep_run_chunk(const OpenLoopNet& net, const std::vector<OpenLoopPoin
 // registers, LDS and scratch of the kernel (code-object metadata through the
 // HIP function attributes); empty without a device
 std::map<std::string, uint64_t> icnt_sweep_kernel_info();
+
+// ---- packet lists and request-reply points (icnt_rr_kernel) ----
+
+// one unit of a launch: a packet list with per-packet sizes on the request
+// subnet (req->nfl) and, with `reply`, its replies on the second subnet,
+// built and ordered on the device (model/icnt_reqreply.h) between the passes
+struct RrUnit {
+  const OpenLoopPoint* req = nullptr;
+  bool reply = false;
+  RtDims d_rep{};                               // the reply pass's dimensions (np = req->np)
+  const std::vector<uint32_t>* kind = nullptr;  // per request: 1 a write, 0 a read
+  uint32_t fl_read = 1, fl_write = 1;           // reply flits by kind
+  uint64_t delay = 0;                           // arrival to reply injection
+};
+
+// what a unit leaves: the request pass and, for a reply unit, the reply
+// schedule and its pass
+struct RrRaw {
+  OpenLoopRaw req, rep;
+  std::vector<uint32_t> reply_of, rep_src, rep_dst, rep_nfl;
+  std::vector<uint64_t> rep_tinj;
+};
+
+uint64_t icnt_rr_unit_bytes(const RrUnit& u);
+
+// one launch: grid = the chunk's units, 64 lanes each, both subnets of a unit
+// in the one workgroup.  Same LDS rule and return value as icnt_sweep_run_chunk.
+bool icnt_rr_run_chunk(const OpenLoopNet& net, const std::vector<RrUnit>& units, uint64_t step_cap, bool allow_lds,
+                       std::vector<RrRaw>& raws);
+
+std::map<std::string, uint64_t> icnt_rr_kernel_info();
 
 }  // namespace asim
