@@ -25,7 +25,11 @@ subnet (``read_request_size`` .. ``write_reply_size`` and ``write_fraction``
 from the ``.icnt`` file, Booksim's names; ``--mem-nodes M`` makes the last M
 nodes the memory partitions every request goes to).  ``--replay FILE`` runs a
 packet list of the user's (an ``.npz`` with ``src``, ``dst``, ``flits``,
-``tinj``), for example one dumped from a cycle simulation.
+``tinj``), for example one dumped from a cycle simulation; FILE may also be
+the capture file itself (``-icnt_capture``, icnt/capture.py; ``--subnet``
+picks the subnet), and ``--networks a.icnt,b.icnt,...`` replays the one list
+on every network of the list, each with its own flit counts from the packets'
+bytes (``--engine gpu``: one wavefront per network in one launch).
 """
 from __future__ import annotations
 
@@ -80,6 +84,67 @@ def replay(icnt_text: str, src, dst, flits, tinj, engine: str = "cpu", cycles: i
     mod = _native.load(prefer_torch_runtime=engine == "gpu")
     return dict(mod.icnt_replay_batch(icnt_text, [(src, dst, flits, tinj)], engine=engine, arrivals=arrivals,
                                       mem_budget_mb=mem_budget_mb, cycles=cycles, warmup=warmup)[0])
+
+
+def replay_networks(src, dst, nbytes, tinj, icnt_texts: List[str], engine: str = "cpu", cycles: int = 0,
+                    warmup: int = 0, arrivals: bool = False, mem_budget_mb: int = 0, lds: bool = True,
+                    nodes: int = 0) -> List[Dict[str, float]]:
+    """One packet list through many networks, one result per ``.icnt`` text:
+    packet i weighs ``nbytes[i]`` bytes and every network derives its own flit
+    count from that.  ``engine="gpu"`` runs one wavefront per network, as many
+    networks per launch as the memory budget takes
+    (csrc/engine/icnt_net_sweep.hip).  `nodes`: the list's node count; a
+    network with another one is refused (0: not checked)."""
+    mod = _native.load(prefer_torch_runtime=engine == "gpu")
+    return [dict(d) for d in mod.icnt_replay_networks((src, dst, nbytes, tinj), list(icnt_texts), engine=engine,
+                                                      arrivals=arrivals, mem_budget_mb=mem_budget_mb, lds=lds,
+                                                      cycles=cycles, warmup=warmup, nodes=nodes)]
+
+
+def _replay_lists(path: str, subnet: str):
+    """[(label, src, dst, bytes or None, flits, tinj, nodes)] of a --replay
+    file: the chosen subnets of a capture file, or the one list of an .npz."""
+    import numpy as np
+    from . import capture
+    if capture.is_capture(path):
+        cap = capture.load(path)
+        names = capture.SUBNETS if subnet == "both" else (subnet,)
+        return [(n, s.src, s.dst, s.bytes, s.flits, s.tinj, cap.nodes) for n in names for s in (cap.subnet(n),)]
+    with np.load(path) as z:
+        return [(None, z["src"], z["dst"], z["bytes"] if "bytes" in z else None, z["flits"], z["tinj"],
+                 int(z["nodes"]) if "nodes" in z else 0)]
+
+
+def _main_replay(a) -> int:
+    lists = _replay_lists(a.replay, a.subnet)
+    nets = [n for n in (a.networks or "").split(",") if n]
+    out = []
+    for label, src, dst, nbytes, flits, tinj, nodes in lists:
+        what = f"{a.replay}" + (f" ({label} subnet)" if label else "")
+        if nets or (label and a.config):
+            # a capture file, or several networks: every network's own flits from the bytes
+            if nbytes is None:
+                print("--networks needs a packet list with bytes (a capture file, or an .npz with a bytes array)",
+                      file=sys.stderr)
+                return 2
+            files = nets or [a.config]
+            res = replay_networks(src, dst, nbytes, tinj, [open(f).read() for f in files], engine=a.engine,
+                                  cycles=a.cycles or 0, warmup=a.warmup or 0, mem_budget_mb=a.mem_budget_mb,
+                                  nodes=nodes)
+            for f, c in zip(files, res):
+                print(f"====== Replay of {what} on {f} ======")
+                _print_open_loop(c)
+                out.append({"config": f, "replay": a.replay, "subnet": label, "result": c})
+        else:
+            c = replay(open(a.config).read(), src, dst, flits, tinj, engine=a.engine, cycles=a.cycles or 0,
+                       warmup=a.warmup or 0, mem_budget_mb=a.mem_budget_mb)
+            print(f"====== Replay of {what} ======")
+            _print_open_loop(c)
+            out.append({"config": a.config, "replay": a.replay, "result": c})
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out[0] if len(out) == 1 and not nets else out, f, indent=1)
+    return 0
 
 
 def request_reply_sweep(icnt_text: str, rates: List[float], engine: str = "cpu", traffic="uniform",
@@ -215,7 +280,7 @@ def _main_request_reply(a, text: str) -> int:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("config", help="Booksim .icnt file")
+    ap.add_argument("config", nargs="?", help="Booksim .icnt file (optional with --replay FILE --networks ...)")
     ap.add_argument("--traffic", default="uniform",
                     help="uniform, transpose, bitcomp, bitrev, shuffle, tornado, neighbor (comma list)")
     ap.add_argument("--rates", default="0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.8,1.0",
@@ -240,21 +305,25 @@ def main(argv=None) -> int:
                     help="request-reply: the last M nodes are memory partitions, the others issue to them")
     ap.add_argument("--sizes", default=None,
                     help="request-reply: read request, read reply, write request, write reply flits (comma list)")
-    ap.add_argument("--replay", metavar="FILE", help="run the packet list of an .npz (src, dst, flits, tinj)")
+    ap.add_argument("--replay", metavar="FILE",
+                    help="run the packet list of an .npz (src, dst, flits, tinj) or of a cycle simulation's "
+                         "-icnt_capture file")
+    ap.add_argument("--subnet", choices=("request", "reply", "both"), default="request",
+                    help="--replay of a capture file: the subnet (both: two independent replays, one result each)")
+    ap.add_argument("--networks", metavar="A.icnt,B.icnt,...",
+                    help="--replay: the list through each of these networks (in place of the one config), every "
+                         "network with its own flit counts from the packets' bytes; --engine gpu: one launch")
     ap.add_argument("--json", help="write the latency / throughput curve here")
     a = ap.parse_args(argv)
-    text = open(a.config).read()
     if a.replay:
-        import numpy as np
-        with np.load(a.replay) as z:
-            c = replay(text, z["src"], z["dst"], z["flits"], z["tinj"], engine=a.engine, cycles=a.cycles or 0,
-                       warmup=a.warmup or 0, mem_budget_mb=a.mem_budget_mb)
-        print(f"====== Replay of {a.replay} ======")
-        _print_open_loop(c)
-        if a.json:
-            with open(a.json, "w") as f:
-                json.dump({"config": a.config, "replay": a.replay, "result": c}, f, indent=1)
-        return 0
+        if not a.config and not a.networks:
+            ap.error("--replay needs a config or --networks")
+        return _main_replay(a)
+    if not a.config:
+        ap.error("the following arguments are required: config")
+    if a.networks:
+        ap.error("--networks needs --replay")
+    text = open(a.config).read()
     a.cycles = 5000 if a.cycles is None else a.cycles
     a.warmup = 1000 if a.warmup is None else a.warmup
     if a.request_reply:

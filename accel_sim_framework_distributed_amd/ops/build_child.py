@@ -12,8 +12,9 @@ build is exercised in a fresh child with its environment set beforehand
 MANIFEST.json: [{"name", "kernelslist", "preset", "extra"}, ...].  One JSON line
 per application goes to stdout: cycles, instructions, per-kernel cycles, the
 statistics, the SHA-256 of the engine's state image, the kernel variant and
-block count the engine reports for its last launch, and the router pass's
-counters (-sim_router_pass).  The run fails if
+block count the engine reports for its last launch, the router pass's
+counters (-sim_router_pass) and, for an application whose `extra` sets
+-icnt_capture, the capture file's SHA-256.  The run fails if
 that variant is not VARIANT, so a mistyped variable cannot pass as a test of
 the default build.
 """
@@ -34,11 +35,16 @@ def run_app(app: dict) -> dict:
     r = s.run()
     wall = time.perf_counter() - t0
     m = re.search(r"^engine_kernel_variant: (\S+) blocks=(\d+)$", r.output, re.M)
-    return dict(name=app["name"], engine=r.engine, deadlock=r.deadlock, tot_cycle=r.tot_cycle, tot_insn=r.tot_insn,
-                kernel_cycles=[k["cycles"] for k in r.kernels], stats=r.stats,
-                snapshot_sha256=hashlib.sha256(bytes(s.native.snapshot())).hexdigest(),
-                variant=m.group(1) if m else None, blocks=int(m.group(2)) if m else 0, wall_s=round(wall, 3),
-                router_pass=r.router_pass)
+    out = dict(name=app["name"], engine=r.engine, deadlock=r.deadlock, tot_cycle=r.tot_cycle, tot_insn=r.tot_insn,
+               kernel_cycles=[k["cycles"] for k in r.kernels], stats=r.stats,
+               snapshot_sha256=hashlib.sha256(bytes(s.native.snapshot())).hexdigest(),
+               variant=m.group(1) if m else None, blocks=int(m.group(2)) if m else 0, wall_s=round(wall, 3),
+               router_pass=r.router_pass)
+    cap = (app.get("extra") or {}).get("-icnt_capture")
+    if cap:
+        with open(cap, "rb") as f:
+            out["icnt_capture_sha256"] = hashlib.sha256(f.read()).hexdigest()
+    return out
 
 
 def main(argv) -> int:

@@ -53,6 +53,9 @@ class SimResult:
     # -sim_router_pass: mode, passes, max_packets_req / _rep, split_blocks
     # (native Simulator.router_pass_stats)
     router_pass: Dict = dataclasses.field(default_factory=dict)
+    # icnt_capture: records written to the capture file per subnet (0 without one)
+    icnt_capture_request_packets: int = 0
+    icnt_capture_reply_packets: int = 0
 
     @property
     def kips(self) -> float:
@@ -66,8 +69,12 @@ class SimResult:
 
 class Simulator:
     def __init__(self, config: ConfigLike = "QV100", trace: Optional[str] = None, engine: str = "cpu",
-                 extra: Optional[Dict[str, str]] = None, echo: bool = False, torch_runtime: bool = False):
+                 extra: Optional[Dict[str, str]] = None, echo: bool = False, torch_runtime: bool = False,
+                 icnt_capture: Optional[str] = None):
         self.mod = _native.load(prefer_torch_runtime=torch_runtime)
+        if icnt_capture:
+            # every request and reply packet of the run into this file (icnt/capture.py reads it)
+            extra = dict(extra or {}, **{"-icnt_capture": str(icnt_capture)})
         self.args = build_args(config, trace, engine, extra)
         self.native = self.mod.Simulator(self.args, echo)
 
@@ -79,9 +86,12 @@ class Simulator:
         if rc != 0 and not n.deadlock:
             raise RuntimeError("simulation failed:\n" + n.output[-2000:])
         return SimResult(n.tot_insn, n.tot_cycle, wall, n.sim_seconds, n.kernels, n.collectives, n.output,
-                         n.engine, n.deadlock, n.router_pass_stats())
+                         n.engine, n.deadlock, n.router_pass_stats(),
+                         # (absent from an older build of the module loaded through ASIM_NATIVE_SO)
+                         getattr(n, "icnt_capture_request_packets", 0), getattr(n, "icnt_capture_reply_packets", 0))
 
 
 def simulate(trace: str, config: ConfigLike = "QV100", engine: str = "cpu",
-             extra: Optional[Dict[str, str]] = None, echo: bool = False) -> SimResult:
-    return Simulator(config, trace, engine, extra, echo).run()
+             extra: Optional[Dict[str, str]] = None, echo: bool = False,
+             icnt_capture: Optional[str] = None) -> SimResult:
+    return Simulator(config, trace, engine, extra, echo, icnt_capture=icnt_capture).run()

@@ -427,6 +427,56 @@ PYBIND11_MODULE(_asim, m) {
       "engine, one subnet, every packet with its own flit count; the summary's window is [warmup, cycles), "
       "cycles=0: the list's last injection + 1.  ValueError names the list and packet of a bad entry");
   m.def(
+      "icnt_replay_networks",
+      [](const py::tuple& list, const std::vector<std::string>& icnt_texts, const std::string& engine, bool arrivals,
+         uint64_t mem_budget_mb, uint64_t step_cap, bool lds, uint64_t cycles, uint64_t warmup, uint32_t nodes) {
+        typedef py::array_t<uint32_t, py::array::c_style | py::array::forcecast> A32;
+        typedef py::array_t<uint64_t, py::array::c_style | py::array::forcecast> A64;
+        if (list.size() != 4) throw std::invalid_argument("icnt_replay_networks: expected (src, dst, bytes, tinj)");
+        const A32 s = A32::ensure(list[0]), d = A32::ensure(list[1]), b = A32::ensure(list[2]);
+        const A64 ti = A64::ensure(list[3]);
+        if (!s || !d || !b || !ti || s.ndim() != 1 || d.ndim() != 1 || b.ndim() != 1 || ti.ndim() != 1)
+          throw std::invalid_argument("icnt_replay_networks: src, dst, bytes and tinj must be one-dimensional "
+                                      "integer arrays");
+        if ((uint64_t)s.size() > kReplayMaxPackets)
+          throw std::invalid_argument("icnt_replay_networks: too many packets for one pass");
+        ReplayBytesList l;
+        l.nodes = nodes;
+        l.src.assign(s.data(), s.data() + s.size());
+        l.dst.assign(d.data(), d.data() + d.size());
+        l.bytes.assign(b.data(), b.data() + b.size());
+        l.tinj.assign(ti.data(), ti.data() + ti.size());
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<OpenLoopResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_replay_networks(l, icnt_texts, engine, o, cycles, warmup);
+        }
+        py::list out;
+        for (const OpenLoopResult& r : rs) {
+          py::dict dd = open_loop_dict(r);
+          if (arrivals) {
+            dd["arrivals"] = py::array_t<uint64_t>((py::ssize_t)r.arrivals.size(), r.arrivals.data());
+            dd["state"] = py::array_t<uint64_t>((py::ssize_t)r.state.size(), r.state.data());
+          }
+          out.append(dd);
+        }
+        return out;
+      },
+      py::arg("list"), py::arg("icnt_texts"), py::arg("engine") = "cpu", py::arg("arrivals") = false,
+      py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true, py::kw_only(),
+      py::arg("cycles") = 0, py::arg("warmup") = 0, py::arg("nodes") = 0,
+      "one packet list (src, dst, bytes, tinj) through many networks, one result per .icnt text: every network "
+      "derives its own flit counts from the bytes.  nodes: the list's node count (0: not checked).  engine gpu: "
+      "one wavefront per network in one launch (icnt_net_sweep.hip).  ValueError names the network of a bad entry");
+  m.def("icnt_replay_networks_lds_bytes", &icnt_replay_networks_lds_bytes, py::arg("icnt_texts"),
+        "dynamic LDS (bytes) of one gpu launch over these networks: the largest 5 * U * V words among them");
+  m.def("icnt_net_kernel_info", &icnt_net_kernel_info, "registers, LDS and scratch of the network-sweep kernel");
+  m.def(
       "icnt_request_reply_batch",
       [](const std::string& icnt_text, const std::vector<py::dict>& points, const std::string& engine, bool arrivals,
          uint64_t mem_budget_mb, uint64_t step_cap, bool lds) {
@@ -922,6 +972,8 @@ PYBIND11_MODULE(_asim, m) {
       .def_property_readonly("sim_seconds", &Simulator::sim_seconds)
       .def_property_readonly("wall_seconds", &Simulator::wall_seconds)
       .def_property_readonly("deadlock", &Simulator::deadlock)
+      .def_property_readonly("icnt_capture_request_packets", [](const Simulator& s) { return s.icnt_capture_packets(0); })
+      .def_property_readonly("icnt_capture_reply_packets", [](const Simulator& s) { return s.icnt_capture_packets(1); })
       .def_property_readonly("engine", [](Simulator& s) { return std::string(s.engine().name()); })
       .def_property_readonly("config", [](Simulator& s) { return cfg_dict(s.cfg()); })
       .def_property_readonly("kernels",

@@ -366,6 +366,12 @@ const OptDef kOptions[] = {
     {"-sim_router_step_cap", 'u', "0",
      "-sim_router_pass par: loop iterations after which a pass gives up with an error (0 = the pass's own bound; "
      "a diagnostic)"},
+    {"-icnt_capture", 's', "",
+     "write every SM-to-L2 request and L2-to-SM reply packet the cycle engine injects to this file "
+     "(model/icnt_capture.h; replay it with the standalone network mode)"},
+    {"-icnt_capture_buf_kb", 'u', "0",
+     "-icnt_capture: KB of the engine's log per subnet (0 = default; a diagnostic: a small log forces many "
+     "hand-overs, on the GPU engine many launches)"},
     {"-collective_slice_bytes", 'u', "131072", "packet model: bytes per link packet (RCCL slice)"},
     {"-collective_max_channels", 'u', "16", "packet model: max parallel rings (channels)"},
     {"-collective_reduce_gbps", 'f', "900.0", "packet model: local memory bandwidth for reduce/copy (GB/s)"},
@@ -1213,6 +1219,8 @@ DriverOpts derive_driver_opts(const OptionRegistry& r) {
   d.trace_components = r.gets("-trace_components");
   d.trace_sampling_core = (int32_t)r.geti("-trace_sampling_core");
   d.sim_epochs_per_launch = (uint32_t)r.getu("-sim_epochs_per_launch");
+  d.icnt_capture = r.gets("-icnt_capture");
+  d.icnt_capture_buf_kb = r.getu("-icnt_capture_buf_kb");
   {
     const char* env = getenv("GPGPUSIM_DEBUG");
     d.debug = r.getb("-sim_debug") || (env && *env && *env != '0') || r.getu("-sim_break_cycle") > 0;

@@ -104,6 +104,8 @@ struct DriverOpts {
   std::string trace_components;
   int32_t trace_sampling_core = 0;
   uint32_t sim_epochs_per_launch = 4096;
+  std::string icnt_capture;          // -icnt_capture: the capture file ("" = off)
+  uint64_t icnt_capture_buf_kb = 0;  // -icnt_capture_buf_kb
   bool gpu_ingest = true;      // -gpu_ingest: coalesce traces on the GPU engine's device
   uint64_t gpu_ingest_min = 32768;  // -gpu_ingest_min_insts: smaller kernels stay on the host
   bool power_in_loop = true;  // -power_in_loop: engines sample power inside their cycle loop

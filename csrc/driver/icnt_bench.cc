@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <vector>
@@ -742,6 +743,111 @@ std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, cons
       },
       [&](OpenLoopPoint& pt, RrRaw& raw) { finish(pt, raw.req); });
   return out;
+}
+
+std::vector<OpenLoopResult> icnt_replay_networks(const ReplayBytesList& list,
+                                                 const std::vector<std::string>& icnt_texts, const std::string& engine,
+                                                 const OpenLoopBatchOpts& opts, uint64_t cycles, uint64_t warmup) {
+  check_engine("icnt_replay_networks", engine);
+  const size_t n = list.src.size();
+  if (list.dst.size() != n || list.bytes.size() != n || list.tinj.size() != n)
+    throw std::invalid_argument("icnt_replay_networks: src, dst, bytes and tinj differ in length");
+  if (n > kReplayMaxPackets) throw std::invalid_argument("icnt_replay_networks: too many packets for one pass");
+  auto who = [](size_t i) { return "icnt_replay_networks: network " + std::to_string(i); };
+  // the list as network i replays it: that network's flits from the bytes
+  auto flits_for = [&](const OpenLoopNet& net, size_t i) {
+    if (list.nodes && net.N != list.nodes)
+      throw std::invalid_argument(who(i) + " has " + std::to_string(net.N) + " nodes, the packet list is for " +
+                                  std::to_string(list.nodes));
+    const uint32_t max_fl = rt_flits(net.c, kRtMaxPktBytes);
+    ReplayList l;
+    l.src = list.src;
+    l.dst = list.dst;
+    l.tinj = list.tinj;
+    l.flits.resize(n);
+    for (size_t k = 0; k < n; ++k) l.flits[k] = std::min(rt_flits(net.c, list.bytes[k]), max_fl);
+    return l;
+  };
+  std::vector<OpenLoopResult> out;
+  out.reserve(icnt_texts.size());
+  if (engine != "gpu") {
+    for (size_t i = 0; i < icnt_texts.size(); ++i) {
+      try {
+        const ReplayList l = flits_for(icnt_open_loop_net(icnt_texts[i]), i);
+        out.push_back(std::move(icnt_replay_batch(icnt_texts[i], {l}, engine, opts, cycles, warmup)[0]));
+      } catch (const std::invalid_argument& e) {
+        const std::string m = e.what();
+        throw std::invalid_argument(m.rfind(who(i), 0) == 0 ? m : who(i) + ": " + m);
+      }
+    }
+    g_last = OpenLoopBatchStats();
+    return out;
+  }
+  // gpu: the networks are prepared one after the other and packed into
+  // chunks under the memory budget (the list's device copy counts once per
+  // chunk); a full chunk is one launch
+  struct Item {
+    OpenLoopNet net;
+    OpenLoopPoint pt;
+  };
+  const NetList nl{&list.src, &list.dst, &list.bytes, &list.tinj};
+  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb), shared = icnt_net_list_bytes(nl);
+  g_last = OpenLoopBatchStats();
+  g_last.budget_bytes = budget;
+  std::vector<std::unique_ptr<Item>> chunk;
+  uint64_t used = shared;
+  auto flush = [&] {
+    if (chunk.empty()) return;
+    std::vector<NetUnit> units;
+    for (const auto& it : chunk) units.push_back(NetUnit{&it->net, &it->pt});
+    std::vector<OpenLoopRaw> raws;
+    if (icnt_net_run_chunk(nl, units, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
+    ++g_last.chunks;
+    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
+    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
+    for (size_t k = 0; k < chunk.size(); ++k) {
+      check_status(raws[k], out.size(), "icnt_replay_networks: network ");
+      OpenLoopResult r = icnt_open_loop_summarise(chunk[k]->net, chunk[k]->pt, raws[k]);
+      if (opts.arrivals) {
+        r.arrivals = std::move(raws[k].tarr);
+        r.state = std::move(raws[k].state);
+      }
+      out.push_back(std::move(r));
+    }
+    chunk.clear();
+    used = shared;
+  };
+  for (size_t i = 0; i < icnt_texts.size(); ++i) {
+    std::unique_ptr<Item> it(new Item());
+    try {
+      it->net = icnt_open_loop_net(icnt_texts[i]);
+      it->pt = replay_prepare(it->net, flits_for(it->net, i), 0, cycles, warmup);
+    } catch (const std::invalid_argument& e) {
+      const std::string m = e.what();
+      throw std::invalid_argument(m.rfind(who(i), 0) == 0 ? m : who(i) + ": " + m);
+    }
+    const uint64_t need = icnt_net_unit_bytes(NetUnit{&it->net, &it->pt});
+    if (shared + need > budget)
+      throw std::invalid_argument(who(i) + " needs " + std::to_string((shared + need + (1u << 20) - 1) >> 20) +
+                                  " MB, the memory budget is " + std::to_string(budget >> 20) + " MB");
+    if (used + need > budget) flush();
+    used += need;
+    chunk.push_back(std::move(it));
+  }
+  flush();
+  return out;
+}
+
+uint64_t icnt_replay_networks_lds_bytes(const std::vector<std::string>& icnt_texts) {
+  std::vector<OpenLoopNet> nets;
+  std::vector<OpenLoopPoint> pts(icnt_texts.size());
+  for (const std::string& t : icnt_texts) nets.push_back(icnt_open_loop_net(t));
+  std::vector<NetUnit> units;
+  for (size_t i = 0; i < nets.size(); ++i) {
+    pts[i].d = list_dims(nets[i], 1, 1);
+    units.push_back(NetUnit{&nets[i], &pts[i]});
+  }
+  return icnt_net_hot_bytes(units);
 }
 
 std::vector<RequestReplySchedule> icnt_request_reply_schedule(const std::string& icnt_text,

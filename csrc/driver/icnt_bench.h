@@ -122,6 +122,37 @@ std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, cons
                                               const OpenLoopBatchOpts& opts = OpenLoopBatchOpts(),
                                               uint64_t cycles = 0, uint64_t warmup = 0);
 
+// ---- one packet list over many networks ----
+
+// a packet list in bytes (for example a subnet of an -icnt_capture file,
+// model/icnt_capture.h): what a packet weighs in flits depends on the network
+// that replays it.  nodes: the node count the list was made for (0: unknown)
+struct ReplayBytesList {
+  uint32_t nodes = 0;
+  std::vector<uint32_t> src, dst, bytes;
+  std::vector<uint64_t> tinj;
+};
+
+// the list through every network of icnt_texts, one result per network in
+// order.  Network i replays it with
+//   flits = min(rt_flits(c_i, bytes), rt_flits(c_i, kRtMaxPktBytes)).
+// "cpu" is the defining form, a loop of single-network icnt_replay_batch
+// calls; "cpu-par" the lane-parallel pass on the host; "gpu" one wavefront per
+// network, as many networks per launch as the memory budget takes
+// (engine/icnt_net_sweep.hip).  std::invalid_argument, naming the network: a
+// node count other than the list's (when the list states one), or a packet
+// that icnt_replay_batch would refuse.
+std::vector<OpenLoopResult> icnt_replay_networks(const ReplayBytesList& list,
+                                                 const std::vector<std::string>& icnt_texts,
+                                                 const std::string& engine = "cpu",
+                                                 const OpenLoopBatchOpts& opts = OpenLoopBatchOpts(),
+                                                 uint64_t cycles = 0, uint64_t warmup = 0);
+
+// the dynamic LDS (bytes) one gpu launch over these networks takes for the
+// per-(unit, VC) words, the chunk's largest 5 * U * V words: they are in LDS
+// when this fits kIcntSweepLdsBytes.  Host work only.
+uint64_t icnt_replay_networks_lds_bytes(const std::vector<std::string>& icnt_texts);
+
 // ---- request-reply points: two subnets ----
 
 // Reads and writes travel on the request subnet; each one's delivery creates,

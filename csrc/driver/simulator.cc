@@ -28,6 +28,68 @@ static void stat_delta(const std::vector<T>& a, const std::vector<T>& b, std::ve
   }
 }
 
+// -icnt_capture (model/icnt_capture.h): the engine's log arrives piece by
+// piece, so memory stays bounded by the log.  The request subnet's records go
+// straight behind the header; the reply subnet's wait in a side file
+// (FILE.reply.tmp, next to the output) that finish() appends and removes,
+// then the header gets its counts.  run() finishes the file, and so does the
+// destructor (the step API); a process that dies in between leaves the side
+// file and a header without counts, which the loader rejects.  A finished
+// file is not reopened: a second run() of the same Simulator is refused
+// before it simulates anything.
+struct Simulator::CaptureFile : IcntCapSink {
+  std::string path, side;
+  std::fstream main, rep;
+  IcntCapHeader h{};
+  bool done = false;
+  CaptureFile(const std::string& p, const SimCfg& c) : path(p), side(p + ".reply.tmp") {
+    h.magic = kIcntCapMagic;
+    h.version = kIcntCapVersion;
+    h.rec_bytes = sizeof(IcntCapRec);
+    h.nodes = icnt_cap_nodes(c);
+    h.n_clusters = c.n_clusters;
+    h.n_subpart = c.n_subpart;
+    h.flit_size = c.flit_size;
+    h.per_icnt = c.per_icnt;
+    main.open(path, std::ios::binary | std::ios::out | std::ios::in | std::ios::trunc);
+    rep.open(side, std::ios::binary | std::ios::out | std::ios::in | std::ios::trunc);
+    if (!main || !rep) throw std::runtime_error("-icnt_capture: cannot write " + path);
+    main.write(reinterpret_cast<const char*>(&h), sizeof(h));
+  }
+  void put(uint32_t subnet, const IcntCapRec* r, size_t n) override {
+    if (done) throw std::runtime_error("-icnt_capture: the file is closed");
+    (subnet ? rep : main).write(reinterpret_cast<const char*>(r), (std::streamsize)(n * sizeof(IcntCapRec)));
+    h.count[subnet ? 1 : 0] += n;
+    if (!main || !rep) throw std::runtime_error("-icnt_capture: write to " + path + " failed");
+  }
+  void finish() {
+    if (done) return;
+    done = true;
+    rep.flush();
+    rep.seekg(0);
+    std::vector<char> buf(1 << 20);
+    for (uint64_t left = h.count[1] * sizeof(IcntCapRec); left;) {
+      const size_t n = (size_t)std::min<uint64_t>(left, buf.size());
+      rep.read(buf.data(), (std::streamsize)n);
+      main.write(buf.data(), (std::streamsize)n);
+      left -= n;
+    }
+    main.seekp(0);
+    main.write(reinterpret_cast<const char*>(&h), sizeof(h));
+    main.close();
+    rep.close();
+    std::remove(side.c_str());
+  }
+  ~CaptureFile() override {
+    try {
+      finish();
+    } catch (...) {
+    }
+  }
+};
+
+uint64_t Simulator::icnt_capture_packets(uint32_t subnet) const { return capture_ ? capture_->h.count[subnet ? 1 : 0] : 0; }
+
 Simulator::Simulator(const std::vector<std::string>& args) {
   t_start_ = std::chrono::steady_clock::now();
   register_sim_options(reg_);
@@ -78,6 +140,12 @@ Simulator::Simulator(const std::vector<std::string>& args) {
     dbg_.reset(new Debugger(dopt_.debug_script, dopt_.break_cycle, h));
   }
   eng_->init(cfg_);
+  if (!dopt_.icnt_capture.empty()) {
+    capture_.reset(new CaptureFile(dopt_.icnt_capture, cfg_));
+    eng_->capture_arm(capture_.get(), dopt_.icnt_capture_buf_kb);
+  } else if (dopt_.icnt_capture_buf_kb) {
+    throw OptionError("-icnt_capture_buf_kb needs -icnt_capture");
+  }
   per_core_nom_ = cfg_.per_core;
   if (dopt_.power_enabled) {
     power_.reset(new PowerModel());
@@ -155,12 +223,20 @@ double Simulator::wall_seconds() const {
 int Simulator::run() {
   print("Accel-Sim-AMD [MI355X-native trace-driven simulator, engine=%s]\n", eng_->name());
   for (const std::string& w : unmodelled_option_warnings(reg_)) print("GPGPU-Sim: %s\n", w.c_str());
+  if (capture_ && capture_->done)
+    throw std::runtime_error("-icnt_capture: " + capture_->path + " was finished by the first run(); "
+                             "a Simulator captures one run");
   cmds_ = parse_commandlist(dopt_.trace_file);
   next_cmd_ = 0;
   if (dopt_.resume_option) next_cmd_ = resume_checkpoint();
   while (!stop_ && (next_cmd_ < cmds_.size() || !win_.empty())) {
     admit(cmds_.size());
     step();
+  }
+  if (capture_) {
+    capture_->finish();
+    print("icnt_capture: %llu request and %llu reply packets in %s\n", (unsigned long long)capture_->h.count[0],
+          (unsigned long long)capture_->h.count[1], capture_->path.c_str());
   }
   print("GPGPU-Sim: *** simulation thread exiting ***\n");
   print("GPGPU-Sim: *** exit detected ***\n");

@@ -111,6 +111,8 @@ class Simulator {
   const std::vector<KernelResult>& kernels() const { return results_; }
   const std::vector<CollectiveResult>& collectives() const { return colls_; }
   bool deadlock() const { return deadlock_; }
+  // -icnt_capture: records written so far on the request / reply subnet
+  uint64_t icnt_capture_packets(uint32_t subnet) const;
   // analytic collective duration in core cycles
   uint64_t collective_cycles(const Command& c) const;
   // parameters of the packet-level link model (-collective_model packet)
@@ -172,6 +174,9 @@ class Simulator {
   double dvfs_ratio_ = 1.0;
   void set_clock_ratio(double ratio);
   std::unique_ptr<std::ofstream> power_report_, power_trace_, power_steady_, visualizer_;
+  // -icnt_capture: the file writer the engine's capture log drains into
+  struct CaptureFile;
+  std::unique_ptr<CaptureFile> capture_;
   // drain the engine's debug trace events, print the streams the user asked
   // for, return all of them (the debugger evaluates its breakpoints on them)
   std::vector<TraceEv> emit_trace();

@@ -87,6 +87,8 @@ class CheckEngine final : public Engine {
   }
   void stats(std::vector<SMStats>& sm, std::vector<MemStats>& mem) override { a_->stats(sm, mem); }
   RouterPassStats router_pass_stats() override { return a_->router_pass_stats(); }
+  // the primary engine's capture (the reference runs the same epochs)
+  void capture_arm(IcntCapSink* sink, uint64_t buf_kb) override { a_->capture_arm(sink, buf_kb); }
   void snapshot(std::vector<uint8_t>& out) override { a_->snapshot(out); }
   void restore(const std::vector<uint8_t>& in) override {
     a_->restore(in);

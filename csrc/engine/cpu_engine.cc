@@ -26,6 +26,20 @@ uint32_t reply_cap(const SimCfg& c) {
   return (uint32_t)((win + c.per_icnt - 1) / c.per_icnt + 1);
 }
 
+uint32_t icnt_cap_log_records(const SimCfg& c, uint32_t cap_req, uint32_t cap_rep, uint64_t buf_kb) {
+  const uint64_t worst = icnt_cap_epoch_max(c, std::max(cap_req, cap_rep));
+  const uint64_t min_kb = (worst * sizeof(IcntCapRec) + 1023) / 1024;
+  // default: room for kIcntCapDefaultEpochs worst-case epochs within [kIcntCapDefaultKb, kIcntCapMaxDefaultKb]
+  if (!buf_kb)
+    buf_kb = std::max(min_kb, std::min(kIcntCapMaxDefaultKb, std::max(kIcntCapDefaultKb, kIcntCapDefaultEpochs * min_kb)));
+  const uint64_t recs = buf_kb * 1024 / sizeof(IcntCapRec);
+  if (recs < worst)
+    throw std::invalid_argument("-icnt_capture_buf_kb " + std::to_string(buf_kb) +
+                                ": the log must hold one epoch's worst case, " + std::to_string(worst) +
+                                " records per subnet: at least " + std::to_string(min_kb) + " KB");
+  return (uint32_t)std::min<uint64_t>(recs, 0x7fffffffu);
+}
+
 void check_core_clock(const SimCfg& c, uint64_t per_core) {
   if (per_core == 0 || per_core > std::max(c.per_core, c.per_core_max))
     throw std::runtime_error("set_core_clock: core period beyond the configured DVFS range (-dvfs_min_clock_ratio)");
@@ -288,6 +302,17 @@ class CpuEngine : public Engine {
         }
         if (nthr > 1) bar_.wait();
         if (abort.load(std::memory_order_acquire)) break;
+        if (cap_sink_ && tid == 0) {
+          // -icnt_capture: this epoch's mailboxes (parity cur) are complete
+          // after the barrier and no pass has touched their times yet; the
+          // other threads write parity cur again only in epoch e + 2, after
+          // barrier e + 1, which thread 0 reaches after this append
+          try {
+            capture_epoch(cur);
+          } catch (...) {
+            fail();
+          }
+        }
         if (!link_free_.empty()) {
           // shared links of multi-hop routes: this epoch's packets reserve
           // their routes before any destination reads them (icnt_links.h)
@@ -363,6 +388,7 @@ class CpuEngine : public Engine {
     };
     team_.run(nthr, job);
     if (err) std::rethrow_exception(err);
+    if (cap_sink_) capture_flush();
     epoch_ = end_epoch;
     cycle_ = end_cycle;
     if (res.done) {
@@ -487,6 +513,33 @@ class CpuEngine : public Engine {
     *wait_cycles = n_link_state_ ? link_free_[n_link_state_ + 1] : 0;
     if (deadlocked) *deadlocked = n_link_state_ ? link_free_[n_link_state_ + 2] : 0;
   }
+  void capture_arm(IcntCapSink* sink, uint64_t buf_kb) override {
+    uint32_t recs = icnt_cap_log_records(c_, cap_req_, cap_rep_, buf_kb);
+    // the host hands a full log over in the middle of a run, so the default
+    // need not be sized for a launch: one worst-case epoch, or 64 Ki records
+    const uint64_t worst = icnt_cap_epoch_max(c_, std::max(cap_req_, cap_rep_));
+    if (!buf_kb) recs = (uint32_t)std::min<uint64_t>(recs, std::max<uint64_t>(worst, 65536));
+    for (int d = 0; d < 2; ++d) {
+      cap_rec_[d].assign(recs, IcntCapRec{});
+      cap_off_[d].assign((size_t)c_.n_sm * c_.n_subpart, 0);
+      cap_log_[d] = IcntCapLog{cap_rec_[d].data(), cap_off_[d].data(), 0, recs};
+    }
+    cap_sink_ = sink;
+  }
+  // thread 0, after the epoch's barrier: both subnets' mailboxes of parity
+  // cur into the logs, emptied first when the epoch's worst case might not fit
+  void capture_epoch(uint32_t cur) {
+    const uint64_t worst = icnt_cap_epoch_max(c_, std::max(cap_req_, cap_rep_));
+    if (cap_log_[0].n + worst > cap_log_[0].cap || cap_log_[1].n + worst > cap_log_[1].cap) capture_flush();
+    icnt_capture_append<SeqPar>(c_, 0, box_req_[cur].data(), cnt_req_[cur].data(), cap_req_, &cap_log_[0]);
+    icnt_capture_append<SeqPar>(c_, 1, box_rep_[cur].data(), cnt_rep_[cur].data(), cap_rep_, &cap_log_[1]);
+  }
+  void capture_flush() {
+    for (uint32_t d = 0; d < 2; ++d) {
+      if (cap_log_[d].n) cap_sink_->put(d, cap_log_[d].rec, cap_log_[d].n);
+      cap_log_[d].n = 0;
+    }
+  }
   bool router_par() const { return c_.link_contention == 2 && c_.router_pass == 1 && !link_free_.empty(); }
   RouterPassStats router_pass_stats() override {
     RouterPassStats r;
@@ -608,6 +661,11 @@ class CpuEngine : public Engine {
   std::vector<uint32_t> link_refs_;
   size_t n_link_state_ = 0;
   RtPassCount rt_pc_{};  // -sim_router_pass par (thread 0 writes it)
+  // -icnt_capture: the sink and one log per subnet (thread 0 appends)
+  IcntCapSink* cap_sink_ = nullptr;
+  std::vector<IcntCapRec> cap_rec_[2];
+  std::vector<uint32_t> cap_off_[2];
+  IcntCapLog cap_log_[2]{};
   uint64_t epoch_ = 0, cycle_ = 0;
   KernelTab kt_{};
 };

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../model/epoch.h"
+#include "../model/icnt_capture.h"
 #include "../power/power_eval.h"
 #include "../trace/trace.h"
 
@@ -53,6 +54,17 @@ struct RouterPassStats {
 };
 // the message both engines throw when the lane-parallel pass reports RT_STATUS_STEP_CAP
 constexpr const char* kRouterStepCapMsg = "router pass hit its step cap (-sim_router_step_cap / rt_step_cap)";
+
+// where an engine's capture log goes (the driver's file writer)
+struct IcntCapSink {
+  virtual ~IcntCapSink() = default;
+  virtual void put(uint32_t subnet, const IcntCapRec* rec, size_t n) = 0;
+};
+constexpr uint64_t kIcntCapDefaultKb = 4096, kIcntCapMaxDefaultKb = 256 * 1024;  // per subnet
+constexpr uint64_t kIcntCapDefaultEpochs = 256;  // worst-case epochs the default log holds (the GPU engine's launch)
+// records of a subnet's log of buf_kb KB, checked against one epoch's worst
+// case on both subnets (std::invalid_argument names the minimum)
+uint32_t icnt_cap_log_records(const SimCfg& c, uint32_t cap_req, uint32_t cap_rep, uint64_t buf_kb);
 
 class Engine {
  public:
@@ -118,6 +130,15 @@ class Engine {
   // -sim_router_pass: how the router model's epoch pass ran (kept outside the
   // state image; the counts are filled by the lane-parallel pass only)
   virtual RouterPassStats router_pass_stats() { return RouterPassStats{}; }
+  // -icnt_capture (model/icnt_capture.h): from now on every mailbox packet of
+  // the epochs the engine simulates goes to `sink`, per subnet in epoch, cell,
+  // slot order.  The engine keeps a log of `buf_kb` KB per subnet (0: its
+  // default) and hands it over whenever the next epoch might not fit and at
+  // the end of every run(); std::invalid_argument when the log cannot hold
+  // one epoch's worst case.  Outside the state image.
+  virtual void capture_arm(IcntCapSink*, uint64_t /*buf_kb*/) {
+    throw std::runtime_error("engine cannot capture the network traffic");
+  }
   // in-loop power sampling (PwrArm); engines without it return false
   virtual bool power_sampler() const { return false; }
   virtual void power_arm(const PwrArm&) { throw std::runtime_error("engine has no in-loop power sampler"); }

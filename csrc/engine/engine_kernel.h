@@ -59,7 +59,10 @@ struct PwrDev {
   PwrSample* ring;   // [cap] samples of this launch (the host drains after it)
 };
 
-struct GpuArgs {
+// (GpuArgsBase: everything but the capture's block.  The batch kernels, which
+// copy a simulation's arguments from memory and whose host side refuses
+// capture, copy and read only this part.)
+struct GpuArgsBase {
   uint32_t cfg_slot;                 // g_cfg slot of this engine
   const SimCfg* __restrict__ cfg_g;  // global copy (not read by the engine kernel)
   const KernelTab* kt;               // running kernels (copied into LDS at launch)
@@ -92,6 +95,27 @@ struct GpuArgs {
   uint32_t* ework; // [nblocks] work clocks of the last epoch (profiling build)
   PwrDev* pw;      // armed power sampler, or nullptr
 };
+struct GpuArgs : GpuArgsBase {
+  IcntCapDev* cap;  // -icnt_capture: the capture's device block, or nullptr
+};
+
+// -icnt_capture: block `b` appends its share of this epoch's mailboxes
+// (parity cur) to the subnets' logs, lane-parallel (model/icnt_capture.h).
+// d->both: block 0 takes both subnets (it alone runs the link pass, or the
+// simulation has one block); otherwise block 0 the request subnet and block 1
+// the reply subnet, each into a log of its own.  The host bounds a launch's
+// epochs so that the logs cannot overflow.  Out of line, with everything but
+// the block and the parity read from the capture's own block in HBM, and
+// behind a null test of a kernel argument: with capture off the engine's
+// loop pays a scalar compare.  The batch kernels, whose host side refuses
+// capture, compile without the call (engine_body's kCapture).
+template <class P>
+__device__ __attribute__((noinline)) void engine_capture(IcntCapDev* d, uint32_t b, uint32_t cur) {
+  const SimCfg& c = g_cfg[P::uni(d->cfg_slot)];
+  const uint32_t both = P::uni(d->both);
+  if (b == 0) icnt_capture_append<P>(c, 0, d->box[0][cur], d->cnt[0][cur], d->cap[0], &d->log[0]);
+  if (both ? b == 0 : b == 1) icnt_capture_append<P>(c, 1, d->box[1][cur], d->cnt[1][cur], d->cap[1], &d->log[1]);
+}
 
 template <class T>
 __device__ __forceinline__ void copy_state(T* dst, const T* src) {
@@ -279,8 +303,8 @@ __device__ void pwr_evaluate(PwrDev& pw, uint32_t nunits, uint64_t now) {
 
 // the kernel body for block `b` of the simulation `a` (b = blockIdx.x for a
 // single simulation; a batch launch maps its blocks onto several)
-template <class P, bool kSliced, int kMode>
-__device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) {
+template <class P, bool kSliced, int kMode, bool kCapture = true, class A = GpuArgs>
+__device__ __forceinline__ void engine_body(const A& a, const uint32_t b) {
   constexpr bool kGlobal = kMode == kModeGlobal, kSplit = kMode == kModeSplit;
   // The configuration is read all over the model, much of it at lane-varying
   // indices (address-decoder bit runs, per-unit counts, cache geometries
@@ -397,6 +421,15 @@ __device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) 
   // destinations with packets in the previous epoch's mailboxes (all at the
   // launch's first epoch): the gathers of the others are skipped
   uint64_t reqm[2] = {~0ull, ~0ull}, repm[2] = {~0ull, ~0ull};
+  if constexpr (kCapture) {
+    if (a.cap && P::uni(a.cap->carry)) {
+      // -icnt_capture: this launch continues one that the full logs cut short
+      reqm[0] = P::uni(a.cap->mask[0]);
+      reqm[1] = P::uni(a.cap->mask[1]);
+      repm[0] = P::uni(a.cap->mask[2]);
+      repm[1] = P::uni(a.cap->mask[3]);
+    }
+  }
   for (; n < a.max_epochs;) {
     const uint32_t cur = (uint32_t)(epoch & 1), prev = cur ^ 1u;
     const uint64_t t0 = cycle, t1 = t0 + E;
@@ -439,6 +472,19 @@ __device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) 
     }
     uint32_t was_last = 0;
     if (!grid_barrier_b(a.ctl, b, a.nblocks, nbar++, &was_last)) break;
+    if constexpr (kCapture) {
+      // -icnt_capture.  After barrier e the mailboxes of parity cur are
+      // complete and no pass has added a delay to their times.  With a link
+      // model the blocks that run the pass append first (block 0 both
+      // subnets, or under -sim_router_pass par block 0 the request and
+      // block 1 the reply subnet, as in the pass below; the host wrote which
+      // into the capture's block), and every other block waits at the pass's
+      // barrier.  Without one there is no second barrier: parity cur is next
+      // written in epoch e + 2, which a block enters only after barrier
+      // e + 1, and the appending block arrives there only after its append,
+      // so no writer can overtake it.
+      if (a.cap && b < 2) engine_capture<P>(a.cap, b, cur);
+    }
     if (a.link_free) {
       // shared links of multi-hop routes: block 0 walks this epoch's packets
       // in the fixed order (icnt_links.h), then every block waits for it
@@ -517,7 +563,13 @@ __device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) 
     if (P::uni(d.done)) { done = P::uni(d.done); break; }
     if (P::uni(d.deadlock)) { dead = 1; break; }
     if (P::uni(d.limit)) { capped = 1; break; }
-    if (P::uni(d.refill)) break;  // the host streams in more of a kernel's trace
+    if (P::uni(d.refill)) {  // the host streams in more of a kernel's trace
+      // (-icnt_capture: this launch did not end because the logs were full)
+      if constexpr (kCapture) {
+        if (a.cap && b == 0 && (threadIdx.x & 63) == 0) a.cap->stop = 1;
+      }
+      break;
+    }
     if (a.max_cycle && cycle >= a.max_cycle) break;
   }
   P::prof(31);  // launch_rest
@@ -533,6 +585,14 @@ __device__ __forceinline__ void engine_body(const GpuArgs& a, const uint32_t b) 
   if (a.prof && (threadIdx.x & 63) < kProfSlots && (threadIdx.x & 63) != 30) a.prof[(size_t)b * kProfSlots + (threadIdx.x & 63)] += pl->acc[threadIdx.x & 63];
   (void)failed;
   if (a.pw && b == 0 && (threadIdx.x & 63) == 0) a.pw->next = pw_next;
+  if constexpr (kCapture) {
+    if (a.cap && b == 0 && (threadIdx.x & 63) == 0) {
+      a.cap->mask[0] = reqm[0];
+      a.cap->mask[1] = reqm[1];
+      a.cap->mask[2] = repm[0];
+      a.cap->mask[3] = repm[1];
+    }
+  }
   if (b == 0 && (threadIdx.x & 63) == 0) {
     a.ctl->done = done;
     a.ctl->deadlock = dead;

@@ -795,6 +795,7 @@ class GpuEngine : public Engine {
         if (on) BatchLauncher::get().leave();
       }
     } in_run(batch_);
+    cap_win_left_ = epochs_per_launch_;
     for (;;) {
       tw_.ensure(kt_, c_, [&](DispatchView& v) { read_dispatch(v); });
       HIPCHECK(hipMemcpy(d_kt_, &kt_, sizeof(KernelTab), hipMemcpyHostToDevice));
@@ -831,6 +832,12 @@ class GpuEngine : public Engine {
       a.prof = d_prof_;
       a.ework = d_ework_;
       a.pw = pw_on_ ? d_pw_ : nullptr;
+      if (cap_sink_) {
+        // the logs start every launch empty and take cap_epochs_ epochs at
+        // the worst case, so the kernel never has to drop or wait
+        a.cap = d_cap_;
+        a.max_epochs = std::min(cap_win_left_, cap_epochs_);
+      }
       if (batch_) {
         // the launch joins the process's next batch (BatchLauncher)
         a.max_epochs = std::min<uint32_t>(a.max_epochs, BatchLauncher::kBatchEpochs);
@@ -893,6 +900,25 @@ class GpuEngine : public Engine {
       epoch_ = h_ctl_->end_epoch;
       cycle_ = h_ctl_->end_cycle;
       if (pw_on_) pwr_collect();
+      if (cap_sink_) {
+        // a launch that ended only because the logs were full (not at the
+        // window of -sim_epochs_per_launch, a completion, a cap or the run's
+        // limit) is continued: the next launch carries its destination masks
+        // and runs the rest of the window, as the launch without capture does
+        // (the kernel sets `stop` when a trace refill ended the launch, which
+        // may fall on the very epoch the count runs out.  An armed power
+        // sampler never ends a launch: a sample is taken at a barrier of its
+        // own inside the epoch loop, which then goes on, and the sampler's
+        // next point only clamps the epoch decision's fast-forward; the host's
+        // sampling slices end a launch through lim.max_cycle, tested here.)
+        const bool full = h_ctl_->epochs_run == a.max_epochs && a.max_epochs < cap_win_left_;
+        const bool cut = capture_drain([&](bool stop) {
+          return full && !stop && !h_ctl_->done && !h_ctl_->deadlock && !h_ctl_->cap &&
+                 !(lim.max_cycle && cycle_ >= lim.max_cycle) &&
+                 !(lim.max_epochs && res.epochs + h_ctl_->epochs_run >= lim.max_epochs);
+        });
+        cap_win_left_ = cut ? cap_win_left_ - a.max_epochs : epochs_per_launch_;
+      }
       res.epochs += h_ctl_->epochs_run;
       if (h_ctl_->done) {
         res.done = true;
@@ -981,6 +1007,56 @@ class GpuEngine : public Engine {
     *delayed = st[0];
     *wait_cycles = st[1];
     if (deadlocked) *deadlocked = st[2];
+  }
+  void capture_arm(IcntCapSink* sink, uint64_t buf_kb) override {
+    if (batch_)
+      throw std::runtime_error("-icnt_capture: batched launches (ASIM_GPU_BATCH=1) share one kernel among "
+                               "simulations and cannot capture; unset ASIM_GPU_BATCH");
+    cap_recs_ = icnt_cap_log_records(c_, cap_req_, cap_rep_, buf_kb);
+    cap_epochs_ = (uint32_t)std::min<uint64_t>(cap_recs_ / icnt_cap_epoch_max(c_, std::max(cap_req_, cap_rep_)),
+                                               0xffffffffu);
+    IcntCapDev h{};
+    for (int d = 0; d < 2; ++d) {
+      pool_alloc(&d_cap_rec_[d], sizeof(IcntCapRec) * cap_recs_);
+      pool_alloc(&d_cap_off_[d], sizeof(uint32_t) * c_.n_sm * c_.n_subpart);
+      h.log[d] = IcntCapLog{d_cap_rec_[d], d_cap_off_[d], 0, cap_recs_};
+    }
+    for (int p = 0; p < 2; ++p) {
+      h.box[0][p] = d_box_req_[p];
+      h.cnt[0][p] = d_cnt_req_[p];
+      h.box[1][p] = d_box_rep_[p];
+      h.cnt[1][p] = d_cnt_rep_[p];
+    }
+    h.cap[0] = cap_req_;
+    h.cap[1] = cap_rep_;
+    h.cfg_slot = (uint32_t)cfg_slot_;
+    // one block appends both subnets when it alone runs the link pass (every
+    // link model but the router model's lane-parallel pass), or is alone
+    h.both = (nblocks_ < 2 || (d_links_ && !router_par())) ? 1u : 0u;
+    pool_alloc(&d_cap_, sizeof(h));
+    HIPCHECK(hipMemcpy(d_cap_, &h, sizeof(h), hipMemcpyHostToDevice));
+    cap_sink_ = sink;
+  }
+  // after a launch: both logs to the sink, then empty for the next launch
+  // carry(stop): whether the next launch continues this one; returns it
+  template <class F>
+  bool capture_drain(F&& carry) {
+    IcntCapDev h;
+    HIPCHECK(hipMemcpy(&h, d_cap_, sizeof(h), hipMemcpyDeviceToHost));
+    for (uint32_t d = 0; d < 2; ++d) {
+      if (h.log[d].n > cap_recs_) throw std::runtime_error("-icnt_capture: the device log ran over (engine bug)");
+      if (h.log[d].n) {
+        cap_host_.resize(h.log[d].n);
+        HIPCHECK(hipMemcpy(cap_host_.data(), d_cap_rec_[d], sizeof(IcntCapRec) * h.log[d].n, hipMemcpyDeviceToHost));
+        cap_sink_->put(d, cap_host_.data(), h.log[d].n);
+      }
+      h.log[d].n = 0;
+    }
+    const bool c = carry(h.stop != 0);
+    h.carry = c ? 1u : 0u;
+    h.stop = 0;
+    HIPCHECK(hipMemcpy(d_cap_, &h, sizeof(h), hipMemcpyHostToDevice));
+    return c;
   }
   bool router_par() const { return c_.link_contention == 2 && c_.router_pass == 1 && icnt_contention_on(c_); }
   RouterPassStats router_pass_stats() override {
@@ -1201,6 +1277,15 @@ class GpuEngine : public Engine {
     fr(d_link_refs_);
     fr(d_link_refs2_);
     fr(d_rt_pc_);
+    for (int d = 0; d < 2; ++d) {
+      fr(d_cap_rec_[d]);
+      fr(d_cap_off_[d]);
+      d_cap_rec_[d] = nullptr;
+      d_cap_off_[d] = nullptr;
+    }
+    fr(d_cap_);
+    d_cap_ = nullptr;
+    cap_sink_ = nullptr;
     d_link_refs2_ = nullptr;
     d_rt_pc_ = nullptr;
     n_links_ = 0;
@@ -1237,6 +1322,15 @@ class GpuEngine : public Engine {
   uint32_t* d_link_refs2_ = nullptr;  // -sim_router_pass par: block 1's scratch
   RtPassCount* d_rt_pc_ = nullptr;    // and the pass's counters (read by router_pass_stats)
   size_t n_links_ = 0;
+  // -icnt_capture: the subnets' logs in HBM (drained after every launch),
+  // and the epochs of a launch they hold at the worst case
+  IcntCapSink* cap_sink_ = nullptr;
+  IcntCapDev* d_cap_ = nullptr;
+  IcntCapRec* d_cap_rec_[2] = {nullptr, nullptr};
+  uint32_t* d_cap_off_[2] = {nullptr, nullptr};
+  uint32_t cap_recs_ = 0, cap_epochs_ = 0;
+  uint32_t cap_win_left_ = 0;  // epochs left of the launch the run would be in without capture
+  std::vector<IcntCapRec> cap_host_;
   uint32_t ovf_cap_ = 0;
   Pkt* d_box_req_[2] = {nullptr, nullptr};
   uint32_t* d_cnt_req_[2] = {nullptr, nullptr};

@@ -54,4 +54,10 @@ bool icnt_rr_run_chunk(const OpenLoopNet&, const std::vector<RrUnit>&, uint64_t,
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_rr_kernel_info() { return {}; }
+uint64_t icnt_net_unit_bytes(const NetUnit&) { return 0; }
+uint64_t icnt_net_list_bytes(const NetList&) { return 0; }
+bool icnt_net_run_chunk(const NetList&, const std::vector<NetUnit>&, uint64_t, bool, std::vector<OpenLoopRaw>&) {
+  throw std::runtime_error("no GPU engine in this build");
+}
+std::map<std::string, uint64_t> icnt_net_kernel_info() { return {}; }
 }  // namespace asim

@@ -70,4 +70,44 @@ bool icnt_rr_run_chunk(const OpenLoopNet& net, const std::vector<RrUnit>& units,
 
 std::map<std::string, uint64_t> icnt_rr_kernel_info();
 
+// ---- one packet list over many networks (icnt_net_kernel, icnt_net_sweep.hip) ----
+
+// the list every unit of a chunk replays: uploaded once per chunk; a unit's
+// flit counts come from `bytes` and its own network's flit size, on the device
+struct NetList {
+  const std::vector<uint32_t>*src = nullptr, *dst = nullptr, *bytes = nullptr;
+  const std::vector<uint64_t>* tinj = nullptr;
+};
+
+// one unit of a launch: a network and the list as a point of it (pt->nfl: the
+// flit counts the host derived, which the device must reproduce)
+struct NetUnit {
+  const OpenLoopNet* net = nullptr;
+  const OpenLoopPoint* pt = nullptr;
+};
+
+// the dynamic LDS of a chunk's launch: the largest 5 * U * V words among its
+// networks (every workgroup carves its own U * V out of it)
+inline uint64_t icnt_net_hot_bytes(const std::vector<NetUnit>& units) {
+  uint64_t b = 0;
+  for (const NetUnit& u : units) {
+    const uint64_t x = 5ull * u.pt->d.U * u.pt->d.V * 4;
+    b = x > b ? x : b;
+  }
+  return b;
+}
+
+uint64_t icnt_net_unit_bytes(const NetUnit& u);
+uint64_t icnt_net_list_bytes(const NetList& l);
+
+// one launch: grid = the chunk's networks, 64 lanes each; every workgroup
+// reads its own configuration, dimensions and tables from its descriptor.
+// The dynamic LDS is sized for the largest 5 * U * V words of the chunk: in
+// LDS if that fits kIcntSweepLdsBytes (and allow_lds), else in HBM for the
+// whole chunk.  Returns whether they were in LDS.
+bool icnt_net_run_chunk(const NetList& list, const std::vector<NetUnit>& units, uint64_t step_cap, bool allow_lds,
+                        std::vector<OpenLoopRaw>& raws);
+
+std::map<std::string, uint64_t> icnt_net_kernel_info();
+
 }  // namespace asim
