@@ -110,7 +110,7 @@ void host_flush_l2(ChanState* chs, uint32_t nch, const SimCfg& c, bool writeback
         const L2Line* T = l2_tags(ch, c, j);
         for (uint32_t k = 0; k < per_sub; ++k) {
           const L2Line& L = T[k];
-          if (!(L.valid && L.dirty)) continue;
+          if (!L.dirty) continue;  // (dirty sectors of a line with no readable one included: mem.h, difference M1)
           const uint32_t n = (uint32_t)popc64(L.dirty);
           st.l2_mem_wr += n;
           st.l2_mem_wr_req += wr_requests(L.dirty);

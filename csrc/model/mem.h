@@ -7,6 +7,21 @@
 // associative tables so that one wavefront owns one channel on the GPU; the
 // per-domain clocks are integer femtoseconds and are stepped in time order
 // inside each PDES epoch (reference next_clock_domain, gpu-sim.cc:1833-1854).
+//
+// Known difference from the reference, M1 (L2 here, L1 in sm.h): a line's
+// `valid` mask holds its READABLE sectors only.  A store that covers part of
+// a sector and allocates lazily (write-allocate 'L') leaves a way with dirty
+// sectors and no readable one.  The reference keeps such a line MODIFIED:
+// tag_array::probe matches it (a write hits, a read is a SECTOR_MISS on the
+// same way, gpu-cache.cc:269-276) and is_invalid_line() is false, so it is
+// replaced by age like any other.  Here l2_find / l1_find match readable
+// lines only and the victim rule takes a way without readable sectors first:
+// the next access to that line misses and allocates again, and the earlier
+// store's dirty sectors are written back at that point (l2_alloc, l1_evict,
+// host_flush_l2) instead of when the line ages out.  No write is lost; hit /
+// miss and write-back counts of partial-sector stores differ from the
+// reference.  (A write-through L1 keeps no dirty mask: there such a way is
+// simply free again.)  tests/test_memory_oracle.py follows this rule.
 #pragma once
 #include "sm.h"
 
@@ -343,7 +358,8 @@ SIM_HDI int l2_alloc(ChanState& ch, SubPart& sp, const SimCfg& c, uint32_t sub, 
   L2Line* T = l2_tags(ch, c, sub);
   int v = l2_victim<P>(T, g, set);
   L2Line& L = T[set * g.assoc + v];
-  if (L.valid && L.dirty) {
+  // difference M1 (header): a dirty-only victim is written back like any other
+  if (L.dirty) {
     uint32_t nd = (uint32_t)popc64(L.dirty);
     if (!l2dram_can(ch, sp, c, nd)) return -1;
     for (uint32_t s = 0; s < 4; ++s)

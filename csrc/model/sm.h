@@ -585,7 +585,11 @@ SIM_HDI void sm_miss_access_done(S& s, const SimCfg& c, uint32_t w, uint32_t sl,
 }
 
 // ---------------------------------------------------------------------------
-// L1 data cache (sectored, lane-parallel probe over the ways of a set)
+// L1 data cache (sectored, lane-parallel probe over the ways of a set).
+// Known difference from the reference, M1 (see the header of mem.h): `valid`
+// holds readable sectors only, l1_find matches readable lines only, and a way
+// with dirty sectors but no readable one is the first victim; l1_evict writes
+// its dirty sectors back then.
 template <class P, class S>
 SIM_HDI int l1_find(const S& s, const CacheGeom& g, uint32_t set, uint64_t line) {
   const L1Line* base = &s.l1[set * g.assoc];
