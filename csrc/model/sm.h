@@ -10,6 +10,24 @@
 // (scoreboard.cc:83-150 uses std::set), L1 ways are probed lane-parallel, and
 // MSHR waiters live in a flat associative table instead of linked lists
 // (mshr_table, gpu-cache.h:1019).
+//
+// Known differences from the reference in the compute pipeline.  The
+// plain-Python oracle of tests/test_core_oracle.py follows them and says so:
+//   S1  Scheduler start-up.  sched_last[] is zero-filled with the SM and
+//       never reset, so before a scheduler has issued anything its "last
+//       issued warp" is warp 0: the first LRR (and two-level inner) pick of
+//       scheduler 0 starts at warp 1 and wraps to warp 0 last, and GTO /
+//       warp-limiting treat warp 0 as the greedy warp.  The reference's
+//       m_last_supervised_issued starts at end() and its first LRR pick is
+//       the first supervised warp (shader.cc:1249-1556).  Schedulers 1.. only
+//       supervise warps above 0, so their first pick is the reference's.
+//       Like the reference's iterator, sched_last (and fetch_rr, age_ctr)
+//       carries over from CTA to CTA and from kernel to kernel.
+//   S2  Latencies.  The writeback ring holds kWbRing cycles, so a
+//       -trace_opcode_latency_initiation_* latency of kWbRing or more is
+//       refused when the configuration is loaded (sim_options.cc); the clamp
+//       in sm_dispatch is never reached from a loaded configuration.  The
+//       reference sizes its pipelines from the latency instead.
 #pragma once
 #include <stddef.h>
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -1272,7 +1290,7 @@ SIM_HDI void sm_dispatch(S& s, const SmCtx& x, uint64_t now) {
     if ((int32_t)(nf - (uint32_t)now) > 0) continue;  // initiation interval
     uint32_t lat = (uint32_t)(info >> 32) & 0xffffu;
     if (!lat) lat = 1;
-    if (lat >= (uint32_t)kWbRing) lat = kWbRing - 1;
+    if (lat >= (uint32_t)kWbRing) lat = kWbRing - 1;  // S2: refused at load, not reached
     const uint32_t slot = (uint32_t)((now + lat) % kWbRing);
     const uint32_t nwb = P::uni(s.wb_cnt[slot]);
     if (nwb >= wbw) { s.sadd(SK(pipe_stall), 1); continue; }  // result bus busy
