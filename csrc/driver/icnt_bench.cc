@@ -21,14 +21,13 @@
 #include <cstdlib>
 #include <fstream>
 #include <map>
-#include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <vector>
 
 #include "../config/icnt_config.h"
 #include "../engine/engine.h"
-#include "../engine/icnt_sweep.h"
+#include "../engine/icnt_sweep_layout.h"
 #include "../model/icnt_router.h"
 #include "../model/icnt_reqreply.h"
 #include "../model/icnt_router_par.h"
@@ -262,6 +261,58 @@ RtDims list_dims(const OpenLoopNet& net, uint32_t np, uint32_t max_flits) {
   return d;
 }
 
+// a pass's result: its guard status checked (`who` and the index name it),
+// its summary and, on request, its arrivals and state
+OpenLoopResult finish(const char* who, size_t index, const OpenLoopNet& net, const OpenLoopPoint& pt, OpenLoopRaw& raw,
+                      bool arrivals) {
+  check_status(raw, index, who);
+  OpenLoopResult r = icnt_open_loop_summarise(net, pt, raw);
+  if (arrivals) {
+    r.arrivals = std::move(raw.tarr);
+    r.state = std::move(raw.state);
+  }
+  return r;
+}
+
+// gpu: n items are prepared one after the other and packed into chunks under
+// the memory budget; a full chunk is one launch, then finished and dropped.
+// `fixed`: the device bytes of a chunk besides its items.  prep(i): item i;
+// bytes(item): what it adds to a chunk; run(chunk, raws): the launch, true
+// with the per-(unit, VC) words in LDS; done(item, raw): its result.
+// std::invalid_argument, "<subject> <i> needs ...": an item that no chunk holds.
+template <class Item, class Raw, class Prep, class Bytes, class Run, class Done>
+void pack_chunks(const std::string& subject, const OpenLoopBatchOpts& opts, uint64_t fixed, size_t n, Prep prep,
+                 Bytes bytes, Run run, Done done) {
+  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb);
+  g_last = OpenLoopBatchStats();
+  g_last.budget_bytes = budget;
+  std::vector<Item> chunk;
+  uint64_t used = fixed;
+  auto flush = [&] {
+    if (chunk.empty()) return;
+    std::vector<Raw> raws;
+    if (run(chunk, raws)) ++g_last.lds_chunks;
+    ++g_last.chunks;
+    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
+    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
+    for (size_t i = 0; i < chunk.size(); ++i) done(chunk[i], raws[i]);
+    chunk.clear();
+    used = fixed;
+  };
+  for (size_t i = 0; i < n; ++i) {
+    Item it = prep(i);
+    const uint64_t need = bytes(it);
+    if (fixed + need > budget)
+      throw std::invalid_argument(subject + " " + std::to_string(i) + " needs " +
+                                  std::to_string((fixed + need + (1u << 20) - 1) >> 20) + " MB, the memory budget is " +
+                                  std::to_string(budget >> 20) + " MB");
+    if (used + need > budget) flush();
+    used += need;
+    chunk.push_back(std::move(it));
+  }
+  flush();
+}
+
 }  // namespace
 
 OpenLoopNet icnt_open_loop_net(const std::string& icnt_text) {
@@ -419,53 +470,23 @@ std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
   const OpenLoopNet net = icnt_open_loop_net(icnt_text);
   std::vector<OpenLoopResult> out;
   out.reserve(points.size());
-  auto finish = [&](const OpenLoopPoint& pt, OpenLoopRaw& raw) {
-    check_status(raw, out.size());
-    OpenLoopResult r = icnt_open_loop_summarise(net, pt, raw);
-    if (opts.arrivals) {
-      r.arrivals = std::move(raw.tarr);
-      r.state = std::move(raw.state);
-    }
-    out.push_back(std::move(r));
-  };
+  const char* who = "icnt_open_loop_batch: point ";
   g_last = OpenLoopBatchStats();
   if (engine != "gpu") {
     for (const OpenLoopParams& p : points) {
       const OpenLoopPoint pt = icnt_open_loop_prepare(net, p);
       OpenLoopRaw raw = simulate_host(net, pt, engine == "cpu-par", opts.step_cap);
-      finish(pt, raw);
+      out.push_back(finish(who, out.size(), net, pt, raw, opts.arrivals));
     }
     return out;
   }
-  // gpu: points are prepared one after the other and packed into chunks
-  // under the memory budget; a full chunk is launched, summarised and dropped
-  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb);
-  g_last.budget_bytes = budget;
-  std::vector<OpenLoopPoint> chunk;
-  uint64_t used = 0;
-  auto flush = [&] {
-    if (chunk.empty()) return;
-    std::vector<OpenLoopRaw> raws;
-    if (icnt_sweep_run_chunk(net, chunk, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
-    ++g_last.chunks;
-    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
-    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
-    for (size_t i = 0; i < chunk.size(); ++i) finish(chunk[i], raws[i]);
-    chunk.clear();
-    used = 0;
-  };
-  for (size_t i = 0; i < points.size(); ++i) {
-    OpenLoopPoint pt = icnt_open_loop_prepare(net, points[i]);
-    const uint64_t need = icnt_sweep_point_bytes(pt);
-    if (need > budget)
-      throw std::invalid_argument("icnt_open_loop_batch: point " + std::to_string(i) + " needs " +
-                                  std::to_string((need + (1u << 20) - 1) >> 20) + " MB, the memory budget is " +
-                                  std::to_string(budget >> 20) + " MB");
-    if (used + need > budget) flush();
-    used += need;
-    chunk.push_back(std::move(pt));
-  }
-  flush();
+  pack_chunks<OpenLoopPoint, OpenLoopRaw>(
+      "icnt_open_loop_batch: point", opts, icnt_sweep_net_bytes(net), points.size(),
+      [&](size_t i) { return icnt_open_loop_prepare(net, points[i]); }, icnt_sweep_point_bytes,
+      [&](const std::vector<OpenLoopPoint>& chunk, std::vector<OpenLoopRaw>& raws) {
+        return icnt_sweep_run_chunk(net, chunk, opts.step_cap, opts.lds, raws);
+      },
+      [&](OpenLoopPoint& pt, OpenLoopRaw& raw) { out.push_back(finish(who, out.size(), net, pt, raw, opts.arrivals)); });
   return out;
 }
 
@@ -473,41 +494,18 @@ std::vector<OpenLoopResult> icnt_open_loop_batch(const std::string& icnt_text,
 
 namespace {
 
-// gpu: the items are prepared one after the other and packed into chunks under
-// the memory budget; a full chunk is launched, finished and dropped.
-// prep(i): item i; unit(item): its RrUnit; done(item, raw): its result.
+// pack_chunks for the items of icnt_rr_run_chunk; unit(item): its RrUnit
 template <class Item, class Prep, class Unit, class Done>
-void rr_gpu_batch(const std::string& who, const OpenLoopNet& net, size_t n, const OpenLoopBatchOpts& opts, Prep prep,
-                  Unit unit, Done done) {
-  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb);
-  g_last.budget_bytes = budget;
-  std::vector<Item> chunk;
-  uint64_t used = 0;
-  auto flush = [&] {
-    if (chunk.empty()) return;
-    std::vector<RrUnit> units;
-    for (const Item& it : chunk) units.push_back(unit(it));
-    std::vector<RrRaw> raws;
-    if (icnt_rr_run_chunk(net, units, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
-    ++g_last.chunks;
-    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
-    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
-    for (size_t i = 0; i < chunk.size(); ++i) done(chunk[i], raws[i]);
-    chunk.clear();
-    used = 0;
-  };
-  for (size_t i = 0; i < n; ++i) {
-    Item it = prep(i);
-    const uint64_t need = icnt_rr_unit_bytes(unit(it));
-    if (need > budget)
-      throw std::invalid_argument(who + " " + std::to_string(i) + " needs " +
-                                  std::to_string((need + (1u << 20) - 1) >> 20) + " MB, the memory budget is " +
-                                  std::to_string(budget >> 20) + " MB");
-    if (used + need > budget) flush();
-    used += need;
-    chunk.push_back(std::move(it));
-  }
-  flush();
+void rr_gpu_batch(const std::string& subject, const OpenLoopNet& net, size_t n, const OpenLoopBatchOpts& opts,
+                  Prep prep, Unit unit, Done done) {
+  pack_chunks<Item, RrRaw>(
+      subject, opts, icnt_sweep_net_bytes(net), n, prep, [&](const Item& it) { return icnt_rr_unit_bytes(unit(it)); },
+      [&](const std::vector<Item>& chunk, std::vector<RrRaw>& raws) {
+        std::vector<RrUnit> units;
+        for (const Item& it : chunk) units.push_back(unit(it));
+        return icnt_rr_run_chunk(net, units, opts.step_cap, opts.lds, raws);
+      },
+      done);
 }
 
 // a checked packet list as a point of the pass; `index` names it in errors
@@ -715,21 +713,15 @@ std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, cons
   const OpenLoopNet net = icnt_open_loop_net(icnt_text);
   std::vector<OpenLoopResult> out;
   out.reserve(lists.size());
-  auto finish = [&](const OpenLoopPoint& pt, OpenLoopRaw& raw) {
-    check_status(raw, out.size(), "icnt_replay_batch: list ");
-    OpenLoopResult r = icnt_open_loop_summarise(net, pt, raw);
-    if (opts.arrivals) {
-      r.arrivals = std::move(raw.tarr);
-      r.state = std::move(raw.state);
-    }
-    out.push_back(std::move(r));
+  auto done = [&](const OpenLoopPoint& pt, OpenLoopRaw& raw) {
+    out.push_back(finish("icnt_replay_batch: list ", out.size(), net, pt, raw, opts.arrivals));
   };
   g_last = OpenLoopBatchStats();
   if (engine != "gpu") {
     for (size_t i = 0; i < lists.size(); ++i) {
       const OpenLoopPoint pt = replay_prepare(net, lists[i], i, cycles, warmup);
       OpenLoopRaw raw = simulate_host(net, pt, engine == "cpu-par", opts.step_cap);
-      finish(pt, raw);
+      done(pt, raw);
     }
     return out;
   }
@@ -741,7 +733,7 @@ std::vector<OpenLoopResult> icnt_replay_batch(const std::string& icnt_text, cons
         u.req = &pt;
         return u;
       },
-      [&](OpenLoopPoint& pt, RrRaw& raw) { finish(pt, raw.req); });
+      [&](OpenLoopPoint& pt, RrRaw& raw) { done(pt, raw.req); });
   return out;
 }
 
@@ -791,50 +783,28 @@ std::vector<OpenLoopResult> icnt_replay_networks(const ReplayBytesList& list,
     OpenLoopPoint pt;
   };
   const NetList nl{&list.src, &list.dst, &list.bytes, &list.tinj};
-  const uint64_t budget = icnt_sweep_budget_bytes(opts.mem_budget_mb), shared = icnt_net_list_bytes(nl);
-  g_last = OpenLoopBatchStats();
-  g_last.budget_bytes = budget;
-  std::vector<std::unique_ptr<Item>> chunk;
-  uint64_t used = shared;
-  auto flush = [&] {
-    if (chunk.empty()) return;
-    std::vector<NetUnit> units;
-    for (const auto& it : chunk) units.push_back(NetUnit{&it->net, &it->pt});
-    std::vector<OpenLoopRaw> raws;
-    if (icnt_net_run_chunk(nl, units, opts.step_cap, opts.lds, raws)) ++g_last.lds_chunks;
-    ++g_last.chunks;
-    g_last.max_chunk_points = std::max<uint64_t>(g_last.max_chunk_points, chunk.size());
-    g_last.max_chunk_bytes = std::max(g_last.max_chunk_bytes, used);
-    for (size_t k = 0; k < chunk.size(); ++k) {
-      check_status(raws[k], out.size(), "icnt_replay_networks: network ");
-      OpenLoopResult r = icnt_open_loop_summarise(chunk[k]->net, chunk[k]->pt, raws[k]);
-      if (opts.arrivals) {
-        r.arrivals = std::move(raws[k].tarr);
-        r.state = std::move(raws[k].state);
-      }
-      out.push_back(std::move(r));
-    }
-    chunk.clear();
-    used = shared;
-  };
-  for (size_t i = 0; i < icnt_texts.size(); ++i) {
-    std::unique_ptr<Item> it(new Item());
-    try {
-      it->net = icnt_open_loop_net(icnt_texts[i]);
-      it->pt = replay_prepare(it->net, flits_for(it->net, i), 0, cycles, warmup);
-    } catch (const std::invalid_argument& e) {
-      const std::string m = e.what();
-      throw std::invalid_argument(m.rfind(who(i), 0) == 0 ? m : who(i) + ": " + m);
-    }
-    const uint64_t need = icnt_net_unit_bytes(NetUnit{&it->net, &it->pt});
-    if (shared + need > budget)
-      throw std::invalid_argument(who(i) + " needs " + std::to_string((shared + need + (1u << 20) - 1) >> 20) +
-                                  " MB, the memory budget is " + std::to_string(budget >> 20) + " MB");
-    if (used + need > budget) flush();
-    used += need;
-    chunk.push_back(std::move(it));
-  }
-  flush();
+  pack_chunks<Item, OpenLoopRaw>(
+      "icnt_replay_networks: network", opts, icnt_net_list_bytes(nl), icnt_texts.size(),
+      [&](size_t i) {
+        Item it;
+        try {
+          it.net = icnt_open_loop_net(icnt_texts[i]);
+          it.pt = replay_prepare(it.net, flits_for(it.net, i), 0, cycles, warmup);
+        } catch (const std::invalid_argument& e) {
+          const std::string m = e.what();
+          throw std::invalid_argument(m.rfind(who(i), 0) == 0 ? m : who(i) + ": " + m);
+        }
+        return it;
+      },
+      [](const Item& it) { return icnt_net_unit_bytes(NetUnit{&it.net, &it.pt}); },
+      [&](const std::vector<Item>& chunk, std::vector<OpenLoopRaw>& raws) {
+        std::vector<NetUnit> units;
+        for (const Item& it : chunk) units.push_back(NetUnit{&it.net, &it.pt});
+        return icnt_net_run_chunk(nl, units, opts.step_cap, opts.lds, raws);
+      },
+      [&](Item& it, OpenLoopRaw& raw) {
+        out.push_back(finish("icnt_replay_networks: network ", out.size(), it.net, it.pt, raw, opts.arrivals));
+      });
   return out;
 }
 

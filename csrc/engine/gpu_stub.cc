@@ -42,20 +42,16 @@ LaneCheckResult lane_policy_check(const std::string& name, int n, const std::vec
 
 namespace asim {
 // no device: the batch entry point refuses engine "gpu" before it gets here
-uint64_t icnt_sweep_point_bytes(const OpenLoopPoint&) { return 0; }
 uint64_t icnt_sweep_budget_bytes(uint64_t) { throw std::runtime_error("no GPU engine in this build"); }
 bool icnt_sweep_run_chunk(const OpenLoopNet&, const std::vector<OpenLoopPoint>&, uint64_t, bool,
                           std::vector<OpenLoopRaw>&) {
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_sweep_kernel_info() { return {}; }
-uint64_t icnt_rr_unit_bytes(const RrUnit&) { return 0; }
 bool icnt_rr_run_chunk(const OpenLoopNet&, const std::vector<RrUnit>&, uint64_t, bool, std::vector<RrRaw>&) {
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_rr_kernel_info() { return {}; }
-uint64_t icnt_net_unit_bytes(const NetUnit&) { return 0; }
-uint64_t icnt_net_list_bytes(const NetList&) { return 0; }
 bool icnt_net_run_chunk(const NetList&, const std::vector<NetUnit>&, uint64_t, bool, std::vector<OpenLoopRaw>&) {
   throw std::runtime_error("no GPU engine in this build");
 }

@@ -8,48 +8,29 @@
 //   3. the router pass on the reply subnet's state
 // as a loop over the subnet, so the pass is instantiated once per placement
 // of the per-(unit, VC) words, as in icnt_sweep_kernel.  Those words go in LDS
-// under the same kIcntSweepLdsBytes rule; the reply pass reuses them, because
-// a pass initialises them itself and nothing reads them after it.
+// under the same kIcntSweepLdsBytes rule; the reply pass reuses them.
+//
+// This file holds what is particular to these units: the uploaded flit
+// counts, the two-subnet loop and the unit checks.  The chunk's layout is
+// icnt_sweep_layout.h; the pass (sweep_pass), the chunk's device block and
+// copies (SweepChunk) and the resource query are icnt_sweep_dev.h.
 //
 // Every offset and size is computed and bounded on the host (icnt_rr_run_chunk
 // checks each unit before anything is uploaded): a subnet's packets and flits
 // are its RtDims' capacities, every node index is below N, and the kernel
 // indexes only what rt_carve(d) and the unit's three np-word arrays laid out.
-#include <hip/hip_runtime.h>
-
-#include <stdexcept>
-
-#include "engine.h"
-#include "icnt_sweep.h"
-#include "wave_par.h"
+#include "icnt_sweep_dev.h"
 #include "../model/icnt_reqreply.h"
-#include "../model/icnt_router_par.h"
 
 namespace asim {
 
-struct RrPt {
-  RtDims d[2];
-  uint32_t np, nsub;          // packets; subnets to run (1: replay, 2: request-reply)
-  uint32_t fl_read, fl_write;
-  uint64_t delay;
-  uint64_t st_off[2], scr_off[2], aux_off;  // bytes from the chunk's base; aux: kind, reply_of, tmp (np words each)
-};
-struct RrOut {
-  uint64_t act[2][8];
-  uint32_t deadlocked[2], status[2];
-};
-static_assert(RT_ACT_COUNT <= 8, "RrOut holds the activity counters");
-
-#define LDS_AS __attribute__((address_space(3)))
-typedef LDS_AS uint32_t lds_u32;
-
-__global__ __launch_bounds__(64) void icnt_rr_kernel(const SimCfg* cfg, const RrPt* pts, RrOut* outs, char* base,
+__global__ __launch_bounds__(64) void icnt_rr_kernel(const SimCfg* cfg, const RrPt* pts, SweepOut* outs, char* base,
                                                      const uint32_t* rt_off, const uint32_t* rt_links,
                                                      const uint16_t* lat, const uint16_t* inj_lat, uint64_t step_cap,
                                                      int hot_lds) {
   extern __shared__ uint32_t hot_words[];  // hot_lds: 5 * U * V words (the host sized the launch)
   const RrPt pt = pts[blockIdx.x];
-  RrOut* o = outs + blockIdx.x;
+  SweepOut* o = outs + 2 * (size_t)blockIdx.x;  // one record per subnet
   if (!pt.np) return;  // (the chunk was cleared: no activity, nothing lost, status OK)
   uint32_t* aux = reinterpret_cast<uint32_t*>(base + pt.aux_off);
   for (uint32_t sub = 0; sub < pt.nsub; ++sub) {
@@ -65,38 +46,15 @@ __global__ __launch_bounds__(64) void icnt_rr_kernel(const SimCfg* cfg, const Rr
       rt_reply_build<WavePar>(pt.np, RtReplyIn{q.src, q.dst, aux, q.tarr}, RtReplyOut{w.src, w.dst, w.nfl, w.tinj},
                               pt.fl_read, pt.fl_write, pt.delay, aux + pt.np, aux + 2ull * pt.np);
     }
-    uint64_t* st = reinterpret_cast<uint64_t*>(base + pt.st_off[sub]);
-    uint32_t lost = 0;
-    if (hot_lds) {
-      const uint32_t uv = pt.d[sub].U * pt.d[sub].V;
-      lds_u32* h = (lds_u32*)hot_words;
-      const RtHot<lds_u32*> hv{h, h + uv, h + 2 * uv, h + 3 * uv, h + 4 * uv};
-      lost = rt_simulate_par_hot<WavePar>(*cfg, pt.d[sub], st, w, hv, pt.np, o->act[sub], &o->status[sub], step_cap);
-    } else {
-      lost = rt_simulate_par<WavePar>(*cfg, pt.d[sub], st, w, pt.np, o->act[sub], &o->status[sub], step_cap);
-    }
-    WavePar::one([&] { o->deadlocked[sub] = lost; });
+    sweep_pass(*cfg, pt.d[sub], reinterpret_cast<uint64_t*>(base + pt.st_off[sub]), w, pt.np, o + sub, step_cap,
+               hot_lds, hot_words);
     WavePar::sync();
     // a pass cut off by its guard leaves no arrivals to reply to
-    if (WavePar::uni(o->status[sub]) != RT_STATUS_OK) return;
+    if (WavePar::uni(o[sub].status) != RT_STATUS_OK) return;
   }
 }
 
 namespace {
-
-constexpr uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
-
-void hip_ok(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw std::runtime_error(std::string("icnt replay: ") + what + ": " + hipGetErrorString(e));
-}
-
-struct PoolBlock {
-  void* p = nullptr;
-  explicit PoolBlock(size_t bytes) : p(gpu_pool_alloc(bytes)) {}
-  ~PoolBlock() { gpu_pool_release(p); }
-  PoolBlock(const PoolBlock&) = delete;
-  PoolBlock& operator=(const PoolBlock&) = delete;
-};
 
 // std::invalid_argument unless everything the kernel will index lies inside
 // what the unit's dimensions lay out
@@ -127,135 +85,67 @@ void check_unit(const OpenLoopNet& net, const RrUnit& u) {
 
 }  // namespace
 
-uint64_t icnt_rr_unit_bytes(const RrUnit& u) {
-  const OpenLoopPoint& p = *u.req;
-  uint64_t b = align16(rt_state_words(p.d) * 8) + align16(rt_carve(p.d, nullptr, nullptr) * 4) +
-               align16(3ull * p.np * 4) + align16(sizeof(RrPt)) + align16(sizeof(RrOut));
-  if (u.reply) b += align16(rt_state_words(u.d_rep) * 8) + align16(rt_carve(u.d_rep, nullptr, nullptr) * 4);
-  return b;
-}
-
 bool icnt_rr_run_chunk(const OpenLoopNet& net, const std::vector<RrUnit>& units, uint64_t step_cap, bool allow_lds,
                        std::vector<RrRaw>& raws) {
   const size_t n = units.size();
   raws.assign(n, RrRaw());
   if (!n) return false;
-  for (const RrUnit& u : units) check_unit(net, u);
-  // one network per chunk: every unit has the same U and V
-  const RtDims& d0 = units[0].req->d;
-  const uint64_t hot_bytes = 5ull * d0.U * d0.V * 4;
-  for (const RrUnit& u : units)
-    if (u.req->d.U != d0.U || u.req->d.V != d0.V) throw std::invalid_argument("icnt replay: one network per chunk");
-  const bool hot_lds = allow_lds && hot_bytes <= kIcntSweepLdsBytes;
-  // layout: descriptors, results, configuration, anynet tables, then per unit
-  // and subnet state and scratch, and the unit's kind / reply_of / tmp words
+  ChunkLayout l;
+  l.records<RrPt>(n, 2);
+  const NetOff o_net = place_net(l, net);
   std::vector<RrPt> h_pts(n);
-  uint64_t off = 0;
-  auto take = [&](uint64_t bytes) {
-    const uint64_t o = off;
-    off += align16(bytes);
-    return o;
-  };
-  const uint64_t o_pts = take(n * sizeof(RrPt)), o_out = take(n * sizeof(RrOut)), o_cfg = take(sizeof(SimCfg));
-  const uint64_t o_roff = take(net.rt_off.size() * 4), o_rlinks = take(net.rt_links.size() * 4),
-                 o_lat = take(net.lat.size() * 2), o_ilat = take(net.inj_lat.size() * 2);
+  uint64_t hot_bytes = 0, accounted = icnt_sweep_net_bytes(net);
   for (size_t i = 0; i < n; ++i) {
     const RrUnit& u = units[i];
-    RrPt& h = h_pts[i];
-    h = RrPt();
-    h.d[0] = u.req->d;
-    h.d[1] = u.reply ? u.d_rep : u.req->d;
-    h.np = u.req->np;
-    h.nsub = u.reply ? 2 : 1;
-    h.fl_read = u.fl_read;
-    h.fl_write = u.fl_write;
-    h.delay = u.delay;
-    for (uint32_t s = 0; s < h.nsub; ++s) {
-      h.st_off[s] = take(rt_state_words(h.d[s]) * 8);
-      h.scr_off[s] = take(rt_carve(h.d[s], nullptr, nullptr) * 4);
-    }
-    h.aux_off = take(3ull * h.np * 4);
+    check_unit(net, u);
+    // one network per chunk: every unit has the same U and V (its reply subnet too: check_unit)
+    if (u.req->d.U != units[0].req->d.U || u.req->d.V != units[0].req->d.V)
+      throw std::invalid_argument("icnt replay: one network per chunk");
+    h_pts[i] = place_rr_unit(l, u);
+    hot_bytes = std::max(hot_bytes, icnt_hot_bytes(u.req->d));
+    accounted += icnt_rr_unit_bytes(u);
   }
-  PoolBlock blk(off);
-  char* base = static_cast<char*>(blk.p);
-  hip_ok(hipMemset(base, 0, off), "clear the chunk");
-  hip_ok(hipMemcpy(base + o_pts, h_pts.data(), n * sizeof(RrPt), hipMemcpyHostToDevice), "copy descriptors");
-  hip_ok(hipMemcpy(base + o_cfg, &net.c, sizeof(SimCfg), hipMemcpyHostToDevice), "copy configuration");
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    if (bytes) hip_ok(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "copy to the device");
-  };
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    if (bytes) hip_ok(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "copy from the device");
-  };
-  up(base + o_roff, net.rt_off.data(), net.rt_off.size() * 4);
-  up(base + o_rlinks, net.rt_links.data(), net.rt_links.size() * 4);
-  up(base + o_lat, net.lat.data(), net.lat.size() * 2);
-  up(base + o_ilat, net.inj_lat.data(), net.inj_lat.size() * 2);
+  const bool hot_lds = allow_lds && hot_bytes <= kIcntSweepLdsBytes;
+  const SweepChunk ch("icnt replay", l, accounted);
+  ch.up(l.o_pts, h_pts.data(), n * sizeof(RrPt));
+  const SweepChunk::Tables t = ch.up_net(o_net, net);
   std::vector<RtWork> dw(2 * n);  // the subnets' work arrays as device addresses
   for (size_t i = 0; i < n; ++i) {
     const RrUnit& u = units[i];
     const OpenLoopPoint& p = *u.req;
-    for (uint32_t s = 0; s < h_pts[i].nsub; ++s)
-      rt_carve(h_pts[i].d[s], reinterpret_cast<uint32_t*>(base + h_pts[i].scr_off[s]), &dw[2 * i + s]);
+    for (uint32_t s = 0; s < h_pts[i].nsub; ++s) dw[2 * i + s] = device_work(ch, h_pts[i].d[s], h_pts[i].scr_off[s]);
     const size_t np = p.np;
-    up(dw[2 * i].src, p.src.data(), np * 4);
-    up(dw[2 * i].dst, p.dst.data(), np * 4);
-    up(dw[2 * i].nfl, p.nfl.data(), np * 4);
-    up(dw[2 * i].tinj, p.tinj.data(), np * 8);
-    if (u.reply) up(base + h_pts[i].aux_off, u.kind->data(), np * 4);
+    ch.up(dw[2 * i].src, p.src.data(), np * 4);
+    ch.up(dw[2 * i].dst, p.dst.data(), np * 4);
+    ch.up(dw[2 * i].nfl, p.nfl.data(), np * 4);
+    ch.up(dw[2 * i].tinj, p.tinj.data(), np * 8);
+    if (u.reply) ch.up(h_pts[i].aux_off, u.kind->data(), np * 4);
   }
-  const bool an = net.anynet;
   hipLaunchKernelGGL(icnt_rr_kernel, dim3((unsigned)n), dim3(64), hot_lds ? (size_t)hot_bytes : 0, 0,
-                     reinterpret_cast<const SimCfg*>(base + o_cfg), reinterpret_cast<const RrPt*>(base + o_pts),
-                     reinterpret_cast<RrOut*>(base + o_out), base,
-                     an ? reinterpret_cast<const uint32_t*>(base + o_roff) : nullptr,
-                     an ? reinterpret_cast<const uint32_t*>(base + o_rlinks) : nullptr,
-                     an ? reinterpret_cast<const uint16_t*>(base + o_lat) : nullptr,
-                     an ? reinterpret_cast<const uint16_t*>(base + o_ilat) : nullptr, step_cap, hot_lds ? 1 : 0);
-  hip_ok(hipGetLastError(), "launch");
-  hip_ok(hipDeviceSynchronize(), "kernel");
-  std::vector<RrOut> h_out(n);
-  hip_ok(hipMemcpy(h_out.data(), base + o_out, n * sizeof(RrOut), hipMemcpyDeviceToHost), "copy results");
+                     ch.at<const SimCfg>(o_net.cfg), ch.at<const RrPt>(l.o_pts), ch.at<SweepOut>(l.o_out), ch.base(),
+                     t.rt_off, t.rt_links, t.lat, t.inj_lat, step_cap, hot_lds ? 1 : 0);
+  const std::vector<SweepOut> outs = ch.finish(2 * n, l.o_out);
   for (size_t i = 0; i < n; ++i) {
     const size_t np = units[i].req->np;
+    const RrPt& h = h_pts[i];
     RrRaw& r = raws[i];
-    for (uint32_t s = 0; s < h_pts[i].nsub; ++s) {
-      OpenLoopRaw& x = s ? r.rep : r.req;
-      for (int k = 0; k < RT_ACT_COUNT; ++k) x.act[k] = h_out[i].act[s][k];
-      x.deadlocked = h_out[i].deadlocked[s];
-      x.status = h_out[i].status[s];
-      x.state.assign(rt_state_words(h_pts[i].d[s]), 0);
-      down(x.state.data(), base + h_pts[i].st_off[s], x.state.size() * 8);
-      x.tarr.assign(np, 0);
-      down(x.tarr.data(), dw[2 * i + s].tarr, np * 8);
-    }
+    for (uint32_t s = 0; s < h.nsub; ++s)
+      ch.fetch_raw(s ? r.rep : r.req, outs[2 * i + s], h.d[s], h.st_off[s], dw[2 * i + s].tarr, np);
     if (!units[i].reply) continue;
     r.reply_of.assign(np, 0);
     r.rep_src.assign(np, 0);
     r.rep_dst.assign(np, 0);
     r.rep_nfl.assign(np, 0);
     r.rep_tinj.assign(np, 0);
-    down(r.reply_of.data(), base + h_pts[i].aux_off + np * 4, np * 4);
-    down(r.rep_src.data(), dw[2 * i + 1].src, np * 4);
-    down(r.rep_dst.data(), dw[2 * i + 1].dst, np * 4);
-    down(r.rep_nfl.data(), dw[2 * i + 1].nfl, np * 4);
-    down(r.rep_tinj.data(), dw[2 * i + 1].tinj, np * 8);
+    ch.down(r.reply_of.data(), ch.base() + h.aux_off + np * 4, np * 4);
+    ch.down(r.rep_src.data(), dw[2 * i + 1].src, np * 4);
+    ch.down(r.rep_dst.data(), dw[2 * i + 1].dst, np * 4);
+    ch.down(r.rep_nfl.data(), dw[2 * i + 1].nfl, np * 4);
+    ch.down(r.rep_tinj.data(), dw[2 * i + 1].tinj, np * 8);
   }
   return hot_lds;
 }
 
-std::map<std::string, uint64_t> icnt_rr_kernel_info() {
-  std::map<std::string, uint64_t> m;
-  hipFuncAttributes fa;
-  if (!gpu_engine_available() || hipFuncGetAttributes(&fa, (const void*)icnt_rr_kernel) != hipSuccess) {
-    (void)hipGetLastError();
-    return m;
-  }
-  m["num_regs"] = (uint64_t)fa.numRegs;
-  m["scratch_bytes_per_lane"] = (uint64_t)fa.localSizeBytes;
-  m["lds_bytes"] = (uint64_t)fa.sharedSizeBytes;
-  m["max_threads_per_block"] = (uint64_t)fa.maxThreadsPerBlock;
-  return m;
-}
+std::map<std::string, uint64_t> icnt_rr_kernel_info() { return sweep_kernel_info((const void*)icnt_rr_kernel); }
 
 }  // namespace asim

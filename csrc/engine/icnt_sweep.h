@@ -4,9 +4,15 @@
 // (driver/icnt_bench.cc icnt_open_loop_batch) packs the points into chunks
 // under a memory budget; one chunk is one launch.  A second kernel
 // (icnt_rr_sweep.hip) takes packet lists with per-packet sizes and
-// request-reply points, both subnets of a point in one wavefront.  Host-only
-// builds link the stub in gpu_stub.cc.
+// request-reply points, both subnets of a point in one wavefront; a third
+// (icnt_net_sweep.hip) one packet list over many networks.  What the three
+// launch paths share lives in two headers: icnt_sweep_layout.h (plain C++,
+// every build) has a chunk's layout, the descriptors and the `*_bytes` the
+// caller budgets with; icnt_sweep_dev.h (the three .hip files only) has the
+// pass with its LDS placement, the chunk's device block and the resource
+// query.  Host-only builds link the stub in gpu_stub.cc.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -16,17 +22,16 @@
 
 namespace asim {
 
-// device bytes a point takes in a chunk (scratch, state, results)
-uint64_t icnt_sweep_point_bytes(const OpenLoopPoint& pt);
-
 // bytes of one chunk: mem_budget_mb, or kIcntSweepFreeShare of the free
 // device memory when it is 0
 constexpr double kIcntSweepFreeShare = 0.5;  // the rest is left to the process's other engines
 uint64_t icnt_sweep_budget_bytes(uint64_t mem_budget_mb);
 
-// the per-(unit, VC) words of a pass go to LDS when they fit this much (the
-// default dynamic LDS limit of a launch; an 8x8 mesh with 2 VCs takes 15 KB)
+// the per-(unit, VC) words of a pass, 5 * U * V of them, go to LDS when the
+// largest of a chunk fits this much (the default dynamic LDS limit of a
+// launch; an 8x8 mesh with 2 VCs takes 15 KB)
 constexpr uint64_t kIcntSweepLdsBytes = 48 * 1024;
+inline uint64_t icnt_hot_bytes(const RtDims& d) { return 5ull * d.U * d.V * 4; }
 
 // one launch: grid = the chunk's points, 64 lanes each.  raws[i] is point
 // i's arrivals, final state, activity, deadlocked packets and guard status.
@@ -61,8 +66,6 @@ struct RrRaw {
   std::vector<uint64_t> rep_tinj;
 };
 
-uint64_t icnt_rr_unit_bytes(const RrUnit& u);
-
 // one launch: grid = the chunk's units, 64 lanes each, both subnets of a unit
 // in the one workgroup.  Same LDS rule and return value as icnt_sweep_run_chunk.
 bool icnt_rr_run_chunk(const OpenLoopNet& net, const std::vector<RrUnit>& units, uint64_t step_cap, bool allow_lds,
@@ -90,15 +93,9 @@ struct NetUnit {
 // networks (every workgroup carves its own U * V out of it)
 inline uint64_t icnt_net_hot_bytes(const std::vector<NetUnit>& units) {
   uint64_t b = 0;
-  for (const NetUnit& u : units) {
-    const uint64_t x = 5ull * u.pt->d.U * u.pt->d.V * 4;
-    b = x > b ? x : b;
-  }
+  for (const NetUnit& u : units) b = std::max(b, icnt_hot_bytes(u.pt->d));
   return b;
 }
-
-uint64_t icnt_net_unit_bytes(const NetUnit& u);
-uint64_t icnt_net_list_bytes(const NetList& l);
 
 // one launch: grid = the chunk's networks, 64 lanes each; every workgroup
 // reads its own configuration, dimensions and tables from its descriptor.

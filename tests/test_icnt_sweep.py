@@ -155,6 +155,18 @@ def test_gpu_anynet(gpu_native, tmp_path):
     _check_anynet(gpu_native, tmp_path, "gpu")
 
 
+@pytest.mark.gpu
+def test_gpu_anynet_chunks(gpu_native, tmp_path):
+    """The route tables are part of every chunk: the mesh's two points three
+    times over do not fit one 1 MB chunk together with them."""
+    text, points = _anynet(tmp_path)[0]
+    points = points * 3
+    ref = _batch(gpu_native, text, points, "cpu")
+    _same(_batch(gpu_native, text, points, "gpu", mem_budget_mb=1), ref)
+    st = gpu_native.icnt_open_loop_batch_stats()
+    assert st["chunks"] >= 2 and st["max_chunk_bytes"] <= 1 << 20
+
+
 def test_cpu_par_batch_mechanics(native):
     text = _icnt(**MECH_KEYS)
     ref = _reference(native, "mech", text, MECH_POINTS)
