@@ -535,6 +535,8 @@ void parse_dram_timing(SimCfg& c, const std::string& s0) {
   }
   if (!c.nbkgrp) c.nbkgrp = 1;
   if (c.nbk > (uint32_t)kMaxBanksDram) throw OptionError("too many DRAM banks for this build");
+  // ChanState::t_ccdl_ok keeps one tCCDL gate per bank group
+  if (c.nbkgrp > (uint32_t)kMaxBankGroupsDram) throw OptionError("too many DRAM bank groups for this build");
 }
 
 uint8_t sched_of(const std::string& s) {

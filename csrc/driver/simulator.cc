@@ -1113,13 +1113,14 @@ std::vector<TraceEv> Simulator::emit_trace() {
       case EV_SB_RELEASE: return TS_SCOREBOARD;
       case EV_PKT_SEND: case EV_PKT_RECV: return TS_INTERCONNECT;
       case EV_L2_ACCESS: return TS_MEMORY_SUBPARTITION_UNIT;
-      case EV_DRAM_CMD: return TS_MEMORY_PARTITION_UNIT;
+      case EV_DRAM_CMD: case EV_DRAM_ENQ: return TS_MEMORY_PARTITION_UNIT;
       default: return 0;
     }
   };
   auto core_time = [&](const TraceEv& e) -> double {
     if (e.kind == EV_L2_ACCESS) return (double)e.cycle * (double)cfg_.per_l2 / (double)cfg_.per_core;
-    if (e.kind == EV_DRAM_CMD) return (double)e.cycle * (double)cfg_.per_dram / (double)cfg_.per_core;
+    if (e.kind == EV_DRAM_CMD || e.kind == EV_DRAM_ENQ)
+      return (double)e.cycle * (double)cfg_.per_dram / (double)cfg_.per_core;
     return (double)e.cycle;
   };
   std::vector<size_t> idx(ev.size());
@@ -1158,10 +1159,17 @@ std::vector<TraceEv> Simulator::emit_trace() {
         print("GPGPU-Sim Cycle %llu: MEMORY_SUBPARTITION_UNIT - channel %u sub %u L2 %s line 0x%llx\n", cyc,
               e.unit - cfg_.n_sm, e.a >> 8, l2o[e.a & 3], (unsigned long long)e.b);
         break;
+      // the printed cycle is the core clock's; the DRAM lines end with their own
+      // clock's cycle, which the core cycle loses when the DRAM clock is faster
       case EV_DRAM_CMD:
-        print("GPGPU-Sim Cycle %llu: MEMORY_PARTITION_UNIT - channel %u DRAM %s bank %llu row %llu\n", cyc,
-              e.unit - cfg_.n_sm, dcmd[e.a & 3], (unsigned long long)(e.b >> 32),
-              (unsigned long long)(e.b & 0xffffffffull));
+        print("GPGPU-Sim Cycle %llu: MEMORY_PARTITION_UNIT - channel %u DRAM %s bank %llu row %llu dram_cycle %llu\n",
+              cyc, e.unit - cfg_.n_sm, dcmd[e.a & 3], (unsigned long long)(e.b >> 32),
+              (unsigned long long)(e.b & 0xffffffffull), (unsigned long long)e.cycle);
+        break;
+      case EV_DRAM_ENQ:
+        print("GPGPU-Sim Cycle %llu: MEMORY_PARTITION_UNIT - channel %u queues %s bank %llu row %llu dram_cycle %llu\n",
+              cyc, e.unit - cfg_.n_sm, e.a ? "write" : "read", (unsigned long long)(e.b >> 32),
+              (unsigned long long)(e.b & 0xffffffffull), (unsigned long long)e.cycle);
         break;
       default: break;
     }

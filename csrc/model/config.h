@@ -52,6 +52,7 @@ constexpr int kDramLat = 512;       // per channel L2->DRAM latency pipe (in fli
 constexpr int kDramRet = 256;
 constexpr int kMallRet = 64;        // MALL read hits waiting to return to the L2 (per channel)
 constexpr int kMaxBanksDram = 32;
+constexpr int kMaxBankGroupsDram = 8;  // one tCCDL gate each (a power of two)
 constexpr int kMaxSubPerCh = 2;
 constexpr int kMaxSubTot = 128;    // L2 sub-partitions (interconnect destinations)
 constexpr int kMaxSmTot = 512;     // simulated SMs
@@ -109,9 +110,10 @@ enum TraceKind : uint16_t {
   EV_PKT_RECV,       // a = packet type, b = line address
   EV_L2_ACCESS,      // a = sub << 8 | outcome (0 hit, 1 miss, 2 mshr hit, 3 bypass/atomic), b = line
   EV_DRAM_CMD,       // a = command (0 RD, 1 WR, 2 ACT, 3 PRE), b = bank << 32 | row
+  EV_DRAM_ENQ,       // a request enters the DRAM scheduler queue: a = 0 read, 1 write, b = bank << 32 | row
 };
 struct TraceEv {
-  uint64_t cycle;  // core cycle (SM events) or DRAM cycle (DRAM commands) / femtoseconds>>10 (L2)
+  uint64_t cycle;  // core cycle (SM events) or DRAM cycle (DRAM events) / femtoseconds>>10 (L2)
   uint32_t unit;   // SM id, or n_sm + channel id
   uint16_t kind;
   uint16_t a;

@@ -22,6 +22,19 @@
 // miss and write-back counts of partial-sector stores differ from the
 // reference.  (A write-through L1 keeps no dirty mask: there such a way is
 // simply free again.)  tests/test_memory_oracle.py follows this rule.
+//
+// Known difference from the reference, M2 (DRAM scheduler): the reference
+// hands every bank a request of its own (frfcfs_scheduler::schedule per bank:
+// a hit of the bank's open row, else the bank's oldest) and then issues the
+// banks' commands under a round-robin bank priority (dram_t::cycle).  Here
+// dram_cycle arbitrates channel-wide, once for the column command and once
+// for the row command of a cycle: of all queued requests whose gates are
+// open, the oldest wins (age is the arrival sequence q_seq, not the slot).
+// A row with a queued hit is not precharged; with FIFO only the oldest
+// request may issue either command.  The timing gates are the reference's.
+// More than kMaxBankGroupsDram bank groups are refused when the options are
+// loaded (one tCCDL gate per group).  tests/test_dram_oracle.py follows these
+// rules cycle for cycle.
 #pragma once
 #include "sm.h"
 
@@ -159,7 +172,7 @@ struct alignas(16) ChanState {
   uint8_t pad1;
   DramBank bk[kMaxBanksDram];
   uint64_t t_rrd_ok, t_ccd_ok, t_rd_ok, t_wr_ok, bus_free;
-  uint64_t t_ccdl_ok[8];
+  uint64_t t_ccdl_ok[kMaxBankGroupsDram];
   DramRet ret[kDramRet];
   uint32_t ret_head, ret_n;
   uint64_t q_seq;        // arrival sequence for FR-FCFS age order
@@ -706,6 +719,7 @@ template <class P>
 SIM_HDI void dram_cycle(ChanState& ch, const SimCfg& c, const MemCtx& x, uint64_t now_fs) {
   MemStats& st = ch.sp[0].st;
   const uint64_t t = ch.dcycle++;
+  const uint64_t seq0 = ch.q_seq;
   st.dram_cycles++;
   // latency pipe -> (MALL) -> scheduler queue
   while (ch.lat_n) {
@@ -779,6 +793,28 @@ SIM_HDI void dram_cycle(ChanState& ch, const SimCfg& c, const MemCtx& x, uint64_
   }
   st.dram_q_occ += ch.q_n;
   if (ch.q_n == 0) return;
+  // debug trace: the requests that entered the queue in this cycle (from the
+  // latency pipe, and the MALL victims' write-backs), ahead of the cycle's
+  // commands and in arrival order: the event of slot j goes to its arrival
+  // rank among them.  Recorded here and lane-parallel, not with a trace_put
+  // in dram_enqueue: inside the loops above, and even as a serial scan here,
+  // the event costs the engine kernels registers.
+  if (ch.q_seq != seq0 && trace_mem_on(c, TS_MEMORY_PARTITION_UNIT, ch.id)) {
+    const uint32_t unit = c.n_sm + ch.id, n0 = c.trace_cnt[unit];
+    P::each((int)ch.q_hi, [&](int j) {
+      const uint32_t n = n0 + (uint32_t)(ch.q_age[j] - seq0);
+      if (!ch.q_valid[j] || ch.q_age[j] < seq0 || n >= c.trace_cap) return;
+      const DramReq& r = ch.q[j];
+      TraceEv& e = c.trace_ev[(uint64_t)unit * c.trace_cap + n];
+      e.cycle = t;
+      e.unit = unit;
+      e.kind = EV_DRAM_ENQ;
+      e.a = r.write ? 1 : 0;
+      e.b = (uint64_t)r.bank << 32 | r.row;
+    });
+    P::sync();
+    P::one([&] { c.trace_cnt[unit] = n0 + (uint32_t)(ch.q_seq - seq0); });
+  }
   // the scans visit the slots in use only (the empty ones above never qualify)
   const int qn = (int)ch.q_hi;
   const uint32_t burst = amax<uint32_t>(1, c.BL / (c.data_cmd_ratio ? c.data_cmd_ratio : 1));
@@ -787,8 +823,10 @@ SIM_HDI void dram_cycle(ChanState& ch, const SimCfg& c, const MemCtx& x, uint64_
     int o = P::argmin(qn, [&](int i) -> uint64_t { return ch.q_valid[i] ? ch.q_age[i] : ~0ull; });
     if (o < 0 || t < ch.t_ccd_ok) return;
     const DramReq r = ch.q[o];
+    if (!r.write && ch.ret_n >= (uint32_t)kDramRet) return;
+    if (trace_mem_on(c, TS_MEMORY_PARTITION_UNIT, ch.id))
+      P::one([&] { trace_put(c, c.n_sm + ch.id, t, EV_DRAM_CMD, r.write ? 1 : 0, (uint64_t)r.bank << 32 | r.row); });
     if (!r.write) {
-      if (ch.ret_n >= (uint32_t)kDramRet) return;
       DramRet& d = ch.ret[(ch.ret_head + ch.ret_n) % kDramRet];
       d.line = r.line;
       d.sector = r.sector;
@@ -837,7 +875,7 @@ SIM_HDI void dram_cycle(ChanState& ch, const SimCfg& c, const MemCtx& x, uint64_
       if (only != 2 && r.write != only) return ~0ull;
       const DramBank& b = ch.bk[r.bank];
       if (!b.open || b.row != r.row || t < b.t_col_ok || t < ch.t_ccd_ok) return ~0ull;
-      if (t < ch.t_ccdl_ok[dram_bkgrp(c, r.bank) & 7]) return ~0ull;
+      if (t < ch.t_ccdl_ok[dram_bkgrp(c, r.bank) & (kMaxBankGroupsDram - 1)]) return ~0ull;
       if (r.write ? (t < ch.t_wr_ok) : (t < ch.t_rd_ok)) return ~0ull;
       return ch.q_age[i];
     });
@@ -863,7 +901,7 @@ SIM_HDI void dram_cycle(ChanState& ch, const SimCfg& c, const MemCtx& x, uint64_
         st.dram_rd++;
       }
       ch.t_ccd_ok = t + amax<uint32_t>(c.tCCD, burst);
-      ch.t_ccdl_ok[dram_bkgrp(c, r.bank) & 7] = t + amax<uint32_t>(c.tCCDL, burst);
+      ch.t_ccdl_ok[dram_bkgrp(c, r.bank) & (kMaxBankGroupsDram - 1)] = t + amax<uint32_t>(c.tCCDL, burst);
       st.dram_busy_cycles += burst;
       ch.q_valid[pick] = 0;
       while (ch.q_hi && !ch.q_valid[ch.q_hi - 1]) --ch.q_hi;
