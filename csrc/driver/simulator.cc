@@ -1155,12 +1155,12 @@ std::vector<TraceEv> Simulator::emit_trace() {
         print("GPGPU-Sim Cycle %llu: INTERCONNECT - core %u ejects packet type %u addr 0x%llx\n", cyc, e.unit, e.a,
               (unsigned long long)e.b);
         break;
+      // the printed cycle is the core clock's; the L2 and DRAM lines end with
+      // their own clock's cycle, which the core cycle loses when that clock is faster
       case EV_L2_ACCESS:
-        print("GPGPU-Sim Cycle %llu: MEMORY_SUBPARTITION_UNIT - channel %u sub %u L2 %s line 0x%llx\n", cyc,
-              e.unit - cfg_.n_sm, e.a >> 8, l2o[e.a & 3], (unsigned long long)e.b);
+        print("GPGPU-Sim Cycle %llu: MEMORY_SUBPARTITION_UNIT - channel %u sub %u L2 %s line 0x%llx l2_cycle %llu\n",
+              cyc, e.unit - cfg_.n_sm, e.a >> 8, l2o[e.a & 3], (unsigned long long)e.b, (unsigned long long)e.cycle);
         break;
-      // the printed cycle is the core clock's; the DRAM lines end with their own
-      // clock's cycle, which the core cycle loses when the DRAM clock is faster
       case EV_DRAM_CMD:
         print("GPGPU-Sim Cycle %llu: MEMORY_PARTITION_UNIT - channel %u DRAM %s bank %llu row %llu dram_cycle %llu\n",
               cyc, e.unit - cfg_.n_sm, dcmd[e.a & 3], (unsigned long long)(e.b >> 32),

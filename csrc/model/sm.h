@@ -28,6 +28,24 @@
 //       refused when the configuration is loaded (sim_options.cc); the clamp
 //       in sm_dispatch is never reached from a loaded configuration.  The
 //       reference sizes its pipelines from the latency instead.
+//
+// Known difference in the interconnect ports (both subnets: sm_receive step 2
+// here, mem_icnt_cycle in mem.h).  The plain-Python oracle of
+// tests/test_icnt_oracle.py follows it and says so:
+//   S3  Port gate.  A crossbar output port arbitrates (xbar_pick) only in a
+//       cycle in which the HEAD of its input queue has arrived
+//       (inq[head].t <= now).  The queue is in (gather epoch, arrival time,
+//       source) order, which is only nearly time order: a multi-flit packet
+//       injected in the last cycles of an epoch (its last flit leaves in the
+//       next one) or, with -network_mode 1, one with a longer pair latency
+//       stands ahead of the next epoch's packets that arrive earlier.  Those
+//       wait for the head although they have reached the port, for at most
+//       the head's flit count - 1 cycles on the crossbar.  The
+//       reference's xbar_router (local_interconnect.cc:123-270) keeps one
+//       buffer per input and grants any input whose own head packet is there,
+//       so another input's late packet never holds it back.  Kept: the head's
+//       time is the port's next-event time (chan_next_event, sm_quiet_until),
+//       one load instead of a scan of the window per idle cycle.
 #pragma once
 #include <stddef.h>
 #if !defined(__HIP_DEVICE_COMPILE__)
