@@ -30,6 +30,22 @@ the capture file itself (``-icnt_capture``, icnt/capture.py; ``--subnet``
 picks the subnet), and ``--networks a.icnt,b.icnt,...`` replays the one list
 on every network of the list, each with its own flit counts from the packets'
 bytes (``--engine gpu``: one wavefront per network in one launch).
+
+``--closed-loop`` runs request-reply traffic with bounded windows (Booksim's
+``sim_type = batch``, batchtrafficmanager.cpp): a node keeps at most
+``--max-outstanding M`` requests in flight (a comma list sweeps M; 0:
+unlimited) and issues the next one when a reply has come back, so the reply
+subnet's arrivals feed the request subnet's injections and both advance on
+one clock (one router pass over the doubled network,
+csrc/model/icnt_closed.h).  ``--batch-size B``: every issuing node creates B
+requests at cycle 0 and the figure is the batch time, the last reply's
+arrival; without it the points are ``--request-reply`` rate points behind the
+window.  The ``.icnt`` keys ``max_outstanding_requests`` and ``batch_size``
+are the defaults, the latter when ``sim_type = batch``.  Unlike Booksim a
+node may issue several requests in one cycle, and a reply leaves from the
+reply subnet's terminal instead of taking its node's injection slot.
+Closed-loop replay of capture files is not offered: a capture does not pair
+replies with requests.
 """
 from __future__ import annotations
 
@@ -187,6 +203,116 @@ def request_reply_sweep(icnt_text: str, rates: List[float], engine: str = "cpu",
     return out
 
 
+def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = None, batch_size: Optional[int] = None,
+                      rates: Optional[List[float]] = None, engine: str = "cpu", traffic="uniform",
+                      cycles: int = 5000, warmup: int = 1000, seed: int = 1, seeds: Optional[List[int]] = None,
+                      write_fraction: Optional[float] = None, reply_delay: int = 0, mem_nodes: int = 0,
+                      read_request_size: Optional[int] = None, read_reply_size: Optional[int] = None,
+                      write_request_size: Optional[int] = None, write_reply_size: Optional[int] = None,
+                      mem_budget_mb: int = 0, arrivals: bool = False, lds: bool = True) -> List[Dict]:
+    """Closed-loop request-reply points with bounded windows as ONE batch
+    through `engine` (``gpu``: one wavefront per point,
+    csrc/engine/icnt_cl_sweep.hip).  A node keeps at most M requests in flight
+    (`max_outstanding`, a list; 0: unlimited) and issues the next one when a
+    reply has come back.  With `rates` the grid is traffic x rate x M x seed
+    of rate points, each the request list of the :func:`request_reply_sweep`
+    point behind the window; otherwise traffic x M x seed of batch points,
+    every issuing node creating `batch_size` requests at cycle 0.  Defaults
+    from the ``.icnt`` keys: ``max_outstanding_requests`` for M, ``batch_size``
+    when ``sim_type = batch``, the four packet sizes and ``write_fraction``.
+
+    Without `arrivals` the result is the curve: one dict per (traffic, rate,
+    M) with the figures averaged over the seeds (``batch_time``,
+    ``round_trip_latency``, ``issue_stall``, ...; maxima: the largest;
+    ``deadlocked``: summed), ``seeds`` and, per seed, ``batch_times``.  With
+    `arrivals` it is one dict per point, in grid order, with its ``traffic``,
+    ``rate``, ``max_outstanding`` and ``seed`` and every array."""
+    mod = _native.load(prefer_torch_runtime=engine == "gpu")
+    kv = mod.parse_booksim_config(icnt_text)
+    given = dict(zip(RR_SIZES, (read_request_size, read_reply_size, write_request_size, write_reply_size)))
+    common = {k: int(v if v is not None else float(kv.get(k, 1))) for k, v in given.items()}
+    common["write_fraction"] = float(write_fraction if write_fraction is not None else kv.get("write_fraction", 0.5))
+    common.update(reply_delay=int(reply_delay), mem_nodes=int(mem_nodes))
+    if "batch_count" in kv:
+        common["batch_count"] = int(float(kv["batch_count"]))
+    if max_outstanding is None:
+        max_outstanding = [int(float(kv.get("max_outstanding_requests", 0)))]
+    if rates is None and batch_size is None:
+        if kv.get("sim_type") != "batch":
+            raise ValueError("closed_loop_sweep needs rates, a batch_size, or sim_type = batch in the .icnt file")
+        batch_size = int(float(kv.get("batch_size", 1)))
+    if rates is None:
+        common["batch_size"] = int(batch_size)
+        rate_list = [None]
+    else:
+        common.update(cycles=int(cycles), warmup=int(warmup))
+        rate_list = list(rates)
+    traffics = [traffic] if isinstance(traffic, str) else list(traffic)
+    seed_list = [seed] if seeds is None else list(seeds)
+    grid = [(t, r, int(m), s) for t in traffics for r in rate_list for m in max_outstanding for s in seed_list]
+    pts = [dict(common, traffic=t, max_outstanding=m, seed=s, **({} if r is None else {"rate": r})) for t, r, m, s in grid]
+    res = mod.icnt_closed_loop_batch(icnt_text, pts, engine=engine, arrivals=arrivals, mem_budget_mb=mem_budget_mb,
+                                     lds=lds)
+    labelled = [dict(d, traffic=t, rate=r, max_outstanding=m, seed=s) for (t, r, m, s), d in zip(grid, res)]
+    if arrivals:
+        return labelled
+    per = len(seed_list)
+    curve = []
+    for lo in range(0, len(labelled), per):
+        group = labelled[lo:lo + per]
+        m = {k: group[0][k] for k in ("traffic", "rate", "max_outstanding", "nodes", "issuers")}
+        m["seeds"] = per
+        for k in ("batch_time", "request_latency", "reply_latency", "round_trip_latency", "issue_stall",
+                  "accepted_request", "accepted_reply", "avg_outstanding", "first_finish", "last_finish", "power_w"):
+            m[k] = sum(p[k] for p in group) / per
+        for k in ("max_round_trip_latency", "max_issue_stall"):
+            m[k] = max(p[k] for p in group)
+        for k in ("requests", "reads", "writes", "deadlocked"):
+            m[k] = sum(p[k] for p in group)
+        m["batch_times"] = [p["batch_time"] for p in group]
+        curve.append(m)
+    return curve
+
+
+def _main_closed_loop(a, text: str) -> int:
+    traffics = [t for t in a.traffic.split(",") if t]
+    seeds = list(range(1, a.seeds + 1)) if a.seeds > 0 else None
+    sizes = dict(zip(RR_SIZES, (int(x) for x in a.sizes.split(",")))) if a.sizes else {}
+    windows = [int(x) for x in a.max_outstanding.split(",") if x] if a.max_outstanding else None
+    rates = [float(x) for x in a.rates.split(",") if x] if a.rates_given else None
+    kv = _native.load().parse_booksim_config(text)
+    batch = a.batch_size
+    if batch is None and rates is None:
+        if kv.get("sim_type") != "batch":
+            print("--closed-loop needs --batch-size, --rates, or sim_type = batch in the .icnt file", file=sys.stderr)
+            return 2
+        batch = int(float(kv.get("batch_size", 1)))
+    curve = closed_loop_sweep(text, windows, batch_size=batch, rates=None if batch is not None else rates,
+                              engine=a.engine, traffic=traffics if len(traffics) > 1 else a.traffic, cycles=a.cycles,
+                              warmup=a.warmup, seed=a.seed, seeds=seeds, write_fraction=a.write_fraction,
+                              reply_delay=a.reply_delay, mem_nodes=a.mem_nodes, mem_budget_mb=a.mem_budget_mb, **sizes)
+    for c in curve:
+        m = c["max_outstanding"]
+        what = f"batch size {batch}" if batch is not None else f"injection rate {c['rate']:.3f}"
+        print(f"====== Traffic {c['traffic']}, closed loop, {what}, max outstanding {m if m else 'unlimited'} ======")
+        if batch is not None:
+            print(f"Batch received. Time used is {c['batch_time']:.0f} cycles "
+                  f"(nodes finish between {c['first_finish']:.0f} and {c['last_finish']:.0f})")
+        print(f"Request average latency = {c['request_latency']:.2f}, reply average latency = {c['reply_latency']:.2f}")
+        print(f"Round-trip average latency = {c['round_trip_latency']:.2f} (max {c['max_round_trip_latency']:.0f}), "
+              f"from the issue")
+        print(f"Issue stall = {c['issue_stall']:.2f} cycles (max {c['max_issue_stall']:.0f}); "
+              f"outstanding requests per node = {c['avg_outstanding']:.2f}")
+        print(f"Accepted rate: request {c['accepted_request']:.4f}, reply {c['accepted_reply']:.4f}")
+        print(f"Packets = {c['reads']} reads, {c['writes']} writes"
+              + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"config": a.config, "traffic": a.traffic, "closed_loop": True, "batch_size": batch,
+                       "reply_delay": a.reply_delay, "mem_nodes": a.mem_nodes, "curve": curve}, f, indent=1)
+    return 0
+
+
 def _mean_rr(points: List[Dict], reply_delay: int) -> Dict[str, float]:
     """The printed figures of one request-reply rate, averaged over its seeds."""
     n = len(points)
@@ -283,8 +409,8 @@ def main(argv=None) -> int:
     ap.add_argument("config", nargs="?", help="Booksim .icnt file (optional with --replay FILE --networks ...)")
     ap.add_argument("--traffic", default="uniform",
                     help="uniform, transpose, bitcomp, bitrev, shuffle, tornado, neighbor (comma list)")
-    ap.add_argument("--rates", default="0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.8,1.0",
-                    help="offered load, flits per node per cycle (comma list)")
+    ap.add_argument("--rates", default=None,
+                    help="offered load, flits per node per cycle (comma list; default 0.05 .. 1.0 in nine steps)")
     ap.add_argument("--packet-flits", type=int, default=1)
     ap.add_argument("--cycles", type=int, default=None, help="default 5000 (--replay: the last injection + 1)")
     ap.add_argument("--warmup", type=int, default=None, help="default 1000 (--replay: 0)")
@@ -305,6 +431,15 @@ def main(argv=None) -> int:
                     help="request-reply: the last M nodes are memory partitions, the others issue to them")
     ap.add_argument("--sizes", default=None,
                     help="request-reply: read request, read reply, write request, write reply flits (comma list)")
+    ap.add_argument("--closed-loop", action="store_true",
+                    help="request-reply traffic with bounded windows: a node issues its next request when a reply "
+                         "has come back (Booksim's sim_type = batch)")
+    ap.add_argument("--max-outstanding", metavar="M,M,...", default=None,
+                    help="closed loop: requests in flight per node, 0 unlimited (comma list; default: the .icnt "
+                         "file's max_outstanding_requests, else unlimited)")
+    ap.add_argument("--batch-size", type=int, default=None,
+                    help="closed loop: every issuing node creates this many requests at cycle 0 (default: the .icnt "
+                         "file's batch_size when its sim_type is batch; else --rates points)")
     ap.add_argument("--replay", metavar="FILE",
                     help="run the packet list of an .npz (src, dst, flits, tinj) or of a cycle simulation's "
                          "-icnt_capture file")
@@ -315,6 +450,11 @@ def main(argv=None) -> int:
                          "network with its own flit counts from the packets' bytes; --engine gpu: one launch")
     ap.add_argument("--json", help="write the latency / throughput curve here")
     a = ap.parse_args(argv)
+    a.rates_given = a.rates is not None
+    if a.rates is None:
+        a.rates = "0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.8,1.0"
+    if a.closed_loop and a.replay:
+        ap.error("--closed-loop cannot replay a packet list: it does not pair replies with requests")
     if a.replay:
         if not a.config and not a.networks:
             ap.error("--replay needs a config or --networks")
@@ -326,6 +466,8 @@ def main(argv=None) -> int:
     text = open(a.config).read()
     a.cycles = 5000 if a.cycles is None else a.cycles
     a.warmup = 1000 if a.warmup is None else a.warmup
+    if a.closed_loop:
+        return _main_closed_loop(a, text)
     if a.request_reply:
         return _main_request_reply(a, text)
     traffics = [t for t in a.traffic.split(",") if t]

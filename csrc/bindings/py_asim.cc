@@ -560,6 +560,109 @@ PYBIND11_MODULE(_asim, m) {
   m.def("icnt_rr_kernel_info", &icnt_rr_kernel_info,
         "registers, LDS and scratch of the replay / request-reply kernel");
   m.def(
+      "icnt_closed_loop_batch",
+      [](const std::string& icnt_text, const std::vector<py::dict>& points, const std::string& engine, bool arrivals,
+         uint64_t mem_budget_mb, uint64_t step_cap, bool lds) {
+        std::vector<ClosedLoopParams> ps;
+        for (const py::dict& d : points) {
+          ClosedLoopParams p;
+          for (const auto& kv : d) {
+            const std::string k = py::cast<std::string>(kv.first);
+            const py::handle v = kv.second;
+            if (k == "traffic") p.traffic = py::cast<std::string>(v);
+            else if (k == "rate") p.rate = py::cast<double>(v);
+            else if (k == "cycles") p.cycles = py::cast<uint64_t>(v);
+            else if (k == "warmup") p.warmup = py::cast<uint64_t>(v);
+            else if (k == "seed") p.seed = py::cast<uint64_t>(v);
+            else if (k == "write_fraction") p.write_fraction = py::cast<double>(v);
+            else if (k == "read_request_size") p.read_request_size = py::cast<uint32_t>(v);
+            else if (k == "read_reply_size") p.read_reply_size = py::cast<uint32_t>(v);
+            else if (k == "write_request_size") p.write_request_size = py::cast<uint32_t>(v);
+            else if (k == "write_reply_size") p.write_reply_size = py::cast<uint32_t>(v);
+            else if (k == "reply_delay") p.reply_delay = py::cast<uint64_t>(v);
+            else if (k == "mem_nodes") p.mem_nodes = py::cast<uint32_t>(v);
+            else if (k == "max_outstanding") p.max_outstanding = py::cast<uint32_t>(v);
+            else if (k == "batch_size") p.batch_size = py::cast<uint32_t>(v);
+            else if (k == "batch_count") p.batch_count = py::cast<uint32_t>(v);
+            else throw std::invalid_argument("icnt_closed_loop_batch: point " + std::to_string(ps.size()) +
+                                             ": unknown field '" + k + "'");
+          }
+          ps.push_back(p);
+        }
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<ClosedLoopResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_closed_loop_batch(icnt_text, ps, engine, o);
+        }
+        auto a32 = [](const std::vector<uint32_t>& v) { return py::array_t<uint32_t>((py::ssize_t)v.size(), v.data()); };
+        auto a64 = [](const std::vector<uint64_t>& v) { return py::array_t<uint64_t>((py::ssize_t)v.size(), v.data()); };
+        const char* an[] = {"buffer_writes", "buffer_reads", "link_flits", "eject_flits", "sa_requests", "credits",
+                            "switch_passes"};
+        py::list out;
+        for (const ClosedLoopResult& r : rs) {
+          py::dict d;
+          d["nodes"] = r.nodes;
+          d["issuers"] = r.issuers;
+          d["requests"] = r.requests;
+          d["measured_requests"] = r.measured;
+          d["reads"] = r.reads;
+          d["writes"] = r.writes;
+          d["batch_time"] = r.batch_time;
+          d["request_latency"] = r.request_latency;
+          d["reply_latency"] = r.reply_latency;
+          d["round_trip_latency"] = r.round_trip_latency;
+          d["max_round_trip_latency"] = r.max_round_trip_latency;
+          d["issue_stall"] = r.issue_stall;
+          d["max_issue_stall"] = r.max_issue_stall;
+          d["accepted_request"] = r.accepted_request;
+          d["accepted_reply"] = r.accepted_reply;
+          d["avg_outstanding"] = r.avg_outstanding;
+          d["first_finish"] = r.first_finish;
+          d["last_finish"] = r.last_finish;
+          d["deadlocked"] = r.deadlocked;
+          py::dict a;
+          for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
+          d["activity"] = a;
+          py::dict e;
+          e["buffer"] = r.e_buffer;
+          e["crossbar"] = r.e_xbar;
+          e["link"] = r.e_link;
+          e["allocator"] = r.e_alloc;
+          e["leakage"] = r.e_leak;
+          d["energy_pj"] = e;
+          d["power_w"] = r.power_w;
+          if (arrivals) {
+            d["request_src"] = a32(r.request_src);
+            d["request_dst"] = a32(r.request_dst);
+            d["request_flits"] = a32(r.request_flits);
+            d["kind"] = a32(r.kind);
+            d["request_tinj"] = a64(r.request_tinj);
+            d["tiss"] = a64(r.tiss);
+            d["request_arrivals"] = a64(r.request_arrivals);
+            d["reply_arrivals"] = a64(r.reply_arrivals);
+            d["state"] = a64(r.state);
+          }
+          out.append(d);
+        }
+        return out;
+      },
+      py::arg("icnt_text"), py::arg("points"), py::arg("engine") = "cpu", py::arg("arrivals") = false,
+      py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true,
+      "closed-loop request-reply points: a node keeps at most max_outstanding requests in flight (0: unlimited) and "
+      "issues the next when a reply has come back; both subnets advance on one clock, one router pass over the "
+      "doubled network.  A point is a dict with the fields of a request-reply point plus max_outstanding and either "
+      "rate / cycles / warmup (the request list of icnt_request_reply_batch) or batch_size (every issuing node "
+      "creates that many requests at cycle 0; batch_time is the last reply's arrival).  arrivals=True adds the "
+      "request list, tiss (issue times), request_arrivals, reply_arrivals (by request) and the state words.  "
+      "ValueError names routing functions min_adapt / valiant, batch_count above 1 and mem_nodes that leave no "
+      "issuer; step_cap is for tests and applies to every engine");
+  m.def("icnt_cl_kernel_info", &icnt_cl_kernel_info, "registers, LDS and scratch of the closed-loop kernel");
+  m.def(
       "arch_energy",
       [](const std::vector<std::string>& args, double node_nm, double vdd, double dram_pj_per_bit,
          double tensor_macs_per_lane) {

@@ -13,7 +13,10 @@
 // (icnt_replay_batch), and request-reply points over two subnets, where a
 // request's arrival creates its reply at the destination (reference
 // trafficmanager.cpp _IssuePacket / _GeneratePacket; icnt_request_reply_batch,
-// model/icnt_reqreply.h).
+// model/icnt_reqreply.h).  The last part is the closed loop: request-reply
+// points whose nodes keep a bounded number of requests in flight, both subnets
+// on one clock in one pass over the doubled network (reference
+// batchtrafficmanager.cpp; icnt_closed_loop_batch, model/icnt_closed.h).
 #include "icnt_bench.h"
 
 #include <algorithm>
@@ -235,6 +238,33 @@ OpenLoopRaw simulate_host(const OpenLoopNet& net, const OpenLoopPoint& pt, bool 
   return raw;
 }
 
+// network energy of a pass from its activity (Booksim power_module.cpp's
+// terms: input buffers, crossbar, channels, allocators, buffer leakage), pJ,
+// and the average power over the cycles to `last`; the per-event energies are
+// .icnt keys with ~22 nm Orion-class defaults
+struct NetEnergy {
+  double buffer, xbar, link, alloc, leak, power_w;
+};
+NetEnergy net_energy(const OpenLoopNet& net, const RtDims& d, const uint64_t* act, uint64_t last) {
+  auto num = [&](const char* k, double dflt) {
+    auto it = net.kv.find(k);
+    return it == net.kv.end() ? dflt : strtod(it->second.c_str(), nullptr);
+  };
+  NetEnergy r;
+  const double bits = 8.0 * net.c.flit_size;
+  r.buffer = num("power_buffer_pj_per_bit", 0.08) * bits * (double)(act[RT_ACT_BUF_WRITE] + act[RT_ACT_BUF_READ]);
+  r.xbar = num("power_xbar_pj_per_bit", 0.06) * bits * (double)act[RT_ACT_BUF_READ];
+  r.link = num("power_link_pj_per_bit_mm", 0.15) * num("power_link_mm", 1.0) * bits *
+           (double)(act[RT_ACT_LINK] + act[RT_ACT_EJECT]);
+  r.alloc = num("power_alloc_pj_per_request", 0.5) * (double)act[RT_ACT_SA_REQ];
+  const double ghz = num("power_clock_ghz", 1.0), t_ns = (double)(last + 1) / ghz;
+  // leakage: uW per buffered flit slot of every input VC
+  r.leak = num("power_buffer_leak_uw_per_flit", 0.5) * 1e-6 * (double)d.U * d.V * d.B * t_ns * 1e3;
+  const double e = r.buffer + r.xbar + r.link + r.alloc + r.leak;
+  r.power_w = t_ns > 0 ? e * 1e-12 / (t_ns * 1e-9) : 0;
+  return r;
+}
+
 OpenLoopBatchStats g_last;  // of the last batch call (one caller at a time)
 
 void check_status(const OpenLoopRaw& raw, size_t index, const char* who = "icnt_open_loop_batch: point ") {
@@ -434,24 +464,13 @@ OpenLoopResult icnt_open_loop_summarise(const OpenLoopNet& net, const OpenLoopPo
   // above saturation the window sees the network before its queues settle;
   // the drain rate is the bottleneck's (open loop, every packet delivered)
   res.drain_throughput = np && last ? (double)total / ((double)N * (double)(last + 1)) : 0;
-  // network energy from the activity (Booksim power_module.cpp's terms:
-  // input buffers, crossbar, channels, allocators, buffer leakage); the
-  // per-event energies are .icnt keys with ~22 nm Orion-class defaults
-  auto num = [&](const char* k, double dflt) {
-    auto it = kv.find(k);
-    return it == kv.end() ? dflt : strtod(it->second.c_str(), nullptr);
-  };
-  const double bits = 8.0 * c.flit_size;
-  res.e_buffer = num("power_buffer_pj_per_bit", 0.08) * bits * (double)(act[RT_ACT_BUF_WRITE] + act[RT_ACT_BUF_READ]);
-  res.e_xbar = num("power_xbar_pj_per_bit", 0.06) * bits * (double)act[RT_ACT_BUF_READ];
-  res.e_link = num("power_link_pj_per_bit_mm", 0.15) * num("power_link_mm", 1.0) * bits *
-               (double)(act[RT_ACT_LINK] + act[RT_ACT_EJECT]);
-  res.e_alloc = num("power_alloc_pj_per_request", 0.5) * (double)act[RT_ACT_SA_REQ];
-  const double ghz = num("power_clock_ghz", 1.0), t_ns = (double)(last + 1) / ghz;
-  // leakage: uW per buffered flit slot of every input VC
-  res.e_leak = num("power_buffer_leak_uw_per_flit", 0.5) * 1e-6 * (double)d.U * d.V * d.B * t_ns * 1e3;
-  const double e = res.e_buffer + res.e_xbar + res.e_link + res.e_alloc + res.e_leak;
-  res.power_w = t_ns > 0 ? e * 1e-12 / (t_ns * 1e-9) : 0;
+  const NetEnergy e = net_energy(net, d, act, last);
+  res.e_buffer = e.buffer;
+  res.e_xbar = e.xbar;
+  res.e_link = e.link;
+  res.e_alloc = e.alloc;
+  res.e_leak = e.leak;
+  res.power_w = e.power_w;
   return res;
 }
 
@@ -554,8 +573,9 @@ struct RrPoint {
   uint64_t reads = 0, writes = 0;
 };
 
-RrPoint rr_prepare(const OpenLoopNet& net, const RequestReplyParams& prm, size_t index) {
-  const std::string who = "icnt_request_reply_batch: point " + std::to_string(index);
+RrPoint rr_prepare(const OpenLoopNet& net, const RequestReplyParams& prm, size_t index,
+                   const char* fn = "icnt_request_reply_batch") {
+  const std::string who = std::string(fn) + ": point " + std::to_string(index);
   const SimCfg& c = net.c;
   const uint32_t N = net.N, M = prm.mem_nodes;
   if (prm.rate < 0 || prm.rate > 1) throw std::invalid_argument(who + ": rate must be 0..1 flits per node per cycle");
@@ -857,6 +877,319 @@ std::vector<RequestReplyResult> icnt_request_reply_batch(const std::string& icnt
       "icnt_request_reply_batch: point", net, points.size(), opts,
       [&](size_t i) { return rr_prepare(net, points[i], i); }, rr_unit,
       [&](RrPoint& pt, RrRaw& raw) { out.push_back(rr_finish(net, pt, raw, opts.arrivals, out.size())); });
+  return out;
+}
+
+// ---- closed-loop points ----
+
+namespace {
+
+// The doubled network of `net`: nodes [0, N) with links [0, L) and a second,
+// disjoint copy on nodes [N, 2N) with links [L, 2L), as a table network.  A
+// built-in topology's routes are enumerated with RtCtx::init_packet itself
+// (bit 31 of a word keeps the torus dateline class; the pass copies table
+// words raw); its channel latency stays uniform (lat / inj_lat empty).
+OpenLoopNet doubled_net(const OpenLoopNet& net) {
+  const char* who = "icnt_closed_loop_batch: ";
+  if (net.c.rt_route == 1 || net.c.rt_route == 2)
+    throw std::invalid_argument(std::string(who) + "routing_function " + (net.c.rt_route == 1 ? "min_adapt" : "valiant") +
+                                " has no route tables (min_adapt and valiant are not modelled in closed loop)");
+  if (net.kv.count("batch_count") && strtoull(net.kv.at("batch_count").c_str(), nullptr, 10) > 1)
+    throw std::invalid_argument(std::string(who) + "batch_count above 1 is not modelled");
+  const uint32_t N = net.N;
+  if (N > kClosedLoopMaxNodes)
+    throw std::invalid_argument(std::string(who) + "the network has " + std::to_string(N) + " nodes, at most " +
+                                std::to_string(kClosedLoopMaxNodes) + " are supported");
+  const RtDims d1 = list_dims(net, 1, 1);
+  const uint32_t L = d1.L;
+  OpenLoopNet b;
+  b.c = net.c;
+  b.kv = net.kv;
+  b.anynet = true;
+  b.N = 2 * N;
+  b.an_L = 2 * L;
+  b.an_H = d1.H;
+  // the single network's routes, pair by pair
+  std::vector<uint32_t> off((size_t)N * N + 1, 0), links;
+  if (net.anynet) {
+    off = net.rt_off;
+    links = net.rt_links;
+  } else {
+    std::vector<uint32_t> scratch(rt_carve(d1, nullptr, nullptr), 0);
+    std::vector<uint64_t> st(rt_state_words(d1), 0);
+    RtWork w;
+    rt_carve(d1, scratch.data(), &w);
+    const RtCtx<RtHot<uint32_t*>> cx(net.c, d1, st.data(), w, RtHot<uint32_t*>{w.vhead, w.vcnt, w.vown, w.vout, w.vocc});
+    for (uint32_t a = 0; a < N; ++a)
+      for (uint32_t t = 0; t < N; ++t) {
+        if (a != t) {
+          w.src[0] = a;
+          w.dst[0] = t;
+          w.nfl[0] = 1;
+          w.tinj[0] = 0;
+          cx.init_packet(0, 0);
+          links.insert(links.end(), w.route, w.route + w.nh[0]);
+        }
+        off[(size_t)a * N + t + 1] = (uint32_t)links.size();
+      }
+  }
+  b.rt_off.assign((size_t)b.N * b.N + 1, 0);
+  b.rt_links.reserve(2 * links.size());
+  for (uint32_t a = 0; a < b.N; ++a)
+    for (uint32_t t = 0; t < b.N; ++t) {
+      const uint32_t sa = a / N, sb = t / N;
+      if (sa == sb) {
+        const size_t p1 = (size_t)(a % N) * N + t % N;
+        for (uint32_t k = off[p1]; k < off[p1 + 1]; ++k) b.rt_links.push_back(links[k] + sa * L);
+      }
+      b.rt_off[(size_t)a * b.N + t + 1] = (uint32_t)b.rt_links.size();
+    }
+  if (net.anynet) {
+    b.lat = net.lat;
+    b.lat.insert(b.lat.end(), net.lat.begin(), net.lat.end());
+    b.inj_lat = net.inj_lat;
+    b.inj_lat.insert(b.inj_lat.end(), net.inj_lat.begin(), net.inj_lat.end());
+  }
+  return b;
+}
+
+// a closed-loop point: the request list with its kinds, then the pass's
+// packets on the doubled network
+struct ClPoint {
+  ClosedLoopParams prm;
+  OpenLoopPoint req;           // on the single network
+  std::vector<uint32_t> kind;  // per request: 1 a write
+  uint64_t reads = 0, writes = 0;
+  uint32_t issuers = 0;
+  RtDims d{};                          // the doubled network's pass
+  std::vector<uint32_t> src, dst, nfl;  // its 2 * nq packets
+};
+
+ClPoint cl_prepare(const OpenLoopNet& net, const OpenLoopNet& dbl, const ClosedLoopParams& prm, size_t index) {
+  const char* fn = "icnt_closed_loop_batch";
+  const std::string who = std::string(fn) + ": point " + std::to_string(index);
+  if (prm.batch_count > 1) throw std::invalid_argument(who + ": batch_count above 1 is not modelled");
+  RequestReplyParams rp;
+  rp.traffic = prm.traffic;
+  rp.rate = prm.batch_size ? 0 : prm.rate;
+  rp.cycles = prm.batch_size ? 1 : prm.cycles;
+  rp.warmup = prm.batch_size ? 0 : prm.warmup;
+  rp.seed = prm.seed;
+  rp.write_fraction = prm.write_fraction;
+  rp.read_request_size = prm.read_request_size;
+  rp.read_reply_size = prm.read_reply_size;
+  rp.write_request_size = prm.write_request_size;
+  rp.write_reply_size = prm.write_reply_size;
+  rp.reply_delay = prm.reply_delay;
+  rp.mem_nodes = prm.mem_nodes;
+  // a rate point's request list is rr_prepare's; a batch point's checks are (rate 0: no packets)
+  RrPoint rr = rr_prepare(net, rp, index, fn);
+  ClPoint pt;
+  pt.prm = prm;
+  const uint32_t N = net.N, M = prm.mem_nodes;
+  pt.issuers = N - M;
+  if (prm.batch_size) {
+    if ((uint64_t)prm.batch_size * pt.issuers > kReplayMaxPackets / 2)
+      throw std::invalid_argument(who + ": too many packets for one pass");
+    OpenLoopPoint& q = rr.req;
+    const SimCfg& c = net.c;
+    Rng r{prm.seed * 0x2545f4914f6cdd1dull + 1};
+    for (uint32_t k = 0; k < prm.batch_size; ++k)
+      for (uint32_t s = 0; s < pt.issuers; ++s) {
+        const uint32_t d = M ? N - M + (uint32_t)(r.next() % M)
+                             : destination(prm.traffic, s, N, net.anynet ? N : c.topo_k, net.anynet ? 1u : c.topo_n, r);
+        if (d == s) continue;  // a fixed point of a permutation sends nothing
+        const uint32_t wr = r.uniform() < prm.write_fraction ? 1u : 0u;
+        q.src.push_back(s);
+        q.dst.push_back(d);
+        q.tinj.push_back(0);
+        q.nfl.push_back(wr ? prm.write_request_size : prm.read_request_size);
+        rr.kind.push_back(wr);
+        ++(wr ? rr.writes : rr.reads);
+      }
+    q.np = (uint32_t)q.src.size();
+  }
+  pt.req = std::move(rr.req);
+  pt.kind = std::move(rr.kind);
+  pt.reads = rr.reads;
+  pt.writes = rr.writes;
+  const uint32_t nq = pt.req.np;
+  if (nq > kReplayMaxPackets / 2) throw std::invalid_argument(who + ": too many packets for one pass");
+  pt.src = pt.req.src;
+  pt.dst = pt.req.dst;
+  pt.nfl = pt.req.nfl;
+  pt.src.resize(2 * (size_t)nq);
+  pt.dst.resize(2 * (size_t)nq);
+  pt.nfl.resize(2 * (size_t)nq);
+  uint64_t flits = 0;
+  for (uint32_t i = 0; i < nq; ++i) {
+    rt_cl_fill_reply(pt.src.data(), pt.dst.data(), pt.nfl.data(), nq, i, N, pt.kind[i], prm.read_reply_size,
+                     prm.write_reply_size);
+    flits += (uint64_t)pt.nfl[i] + pt.nfl[nq + i];
+  }
+  if (flits > 0xffffffffull) throw std::invalid_argument(who + ": too many flits for one pass");
+  pt.d = list_dims(dbl, 2 * nq, 1);
+  pt.d.nf = std::max<uint32_t>(1, (uint32_t)flits);  // exactly the packets' flits
+  return pt;
+}
+
+ClUnit cl_unit(const ClPoint& pt) {
+  ClUnit u;
+  u.d = pt.d;
+  u.nq = pt.req.np;
+  u.window = pt.prm.max_outstanding;
+  u.delay = pt.prm.reply_delay;
+  u.src = &pt.src;
+  u.dst = &pt.dst;
+  u.nfl = &pt.nfl;
+  u.tinj = &pt.req.tinj;
+  return u;
+}
+
+// the closed-loop pass of one point on the host
+ClRaw cl_host(const OpenLoopNet& dbl, const ClPoint& pt, bool par, uint64_t step_cap) {
+  ClRaw raw;
+  const uint32_t nq = pt.req.np;
+  raw.pass.state.assign(rt_state_words(pt.d), 0);
+  raw.tiss.assign(nq, 0);
+  raw.pass.tarr.assign(2 * (size_t)nq, 0);
+  if (!nq) return raw;
+  const uint64_t words = rt_carve(pt.d, nullptr, nullptr);
+  std::vector<uint32_t> scratch(words + rt_cl_carve(pt.d, nq, nullptr, nullptr), 0);
+  RtWork w;
+  rt_carve(pt.d, scratch.data(), &w);
+  RtClosed cl;
+  cl.window = pt.prm.max_outstanding;
+  cl.delay = pt.prm.reply_delay;
+  rt_cl_carve(pt.d, nq, scratch.data() + words, &cl);
+  w.rt_off = dbl.rt_off.data();
+  w.rt_links = dbl.rt_links.data();
+  w.lat = dbl.lat.empty() ? nullptr : dbl.lat.data();
+  w.inj_lat = dbl.inj_lat.empty() ? nullptr : dbl.inj_lat.data();
+  std::copy(pt.src.begin(), pt.src.end(), w.src);
+  std::copy(pt.dst.begin(), pt.dst.end(), w.dst);
+  std::copy(pt.nfl.begin(), pt.nfl.end(), w.nfl);
+  std::copy(pt.req.tinj.begin(), pt.req.tinj.end(), w.tinj);
+  if (par) {
+    const RtHot<uint32_t*> hv{w.vhead, w.vcnt, w.vown, w.vout, w.vocc};
+    raw.pass.deadlocked = rt_simulate_par_closed<SeqPar>(dbl.c, pt.d, raw.pass.state.data(), w, hv, cl, raw.pass.act,
+                                                         &raw.pass.status, step_cap);
+  } else {
+    raw.pass.deadlocked =
+        rt_simulate_closed(dbl.c, pt.d, raw.pass.state.data(), w, cl, raw.pass.act, &raw.pass.status, step_cap);
+  }
+  raw.pass.tarr.assign(w.tarr, w.tarr + 2 * (size_t)nq);
+  raw.tiss.assign(cl.tiss, cl.tiss + nq);
+  return raw;
+}
+
+ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool arrivals, size_t index) {
+  check_status(raw.pass, index, "icnt_closed_loop_batch: point ");
+  const ClosedLoopParams& prm = pt.prm;
+  const uint32_t N = net.N, nq = pt.req.np;
+  const bool batch = prm.batch_size != 0;
+  ClosedLoopResult r;
+  r.nodes = N;
+  r.issuers = pt.issuers;
+  r.requests = nq;
+  r.reads = pt.reads;
+  r.writes = pt.writes;
+  r.deadlocked = raw.pass.deadlocked;
+  for (int i = 0; i < RT_ACT_COUNT; ++i) r.activity[i] = raw.pass.act[i];
+  const std::vector<uint64_t>&tarr = raw.pass.tarr, &tinj = pt.req.tinj;
+  std::vector<uint64_t> finish(N, 0);
+  std::vector<char> has(N, 0);
+  double lq = 0, lp = 0, lr = 0, stall = 0, flight = 0;
+  uint64_t last = 0, ej_req = 0, ej_rep = 0;
+  for (uint32_t i = 0; i < nq; ++i) {
+    const uint64_t ti = raw.tiss[i], aq = tarr[i], ap = tarr[nq + i];
+    last = std::max(last, ap);
+    const uint32_t s = pt.req.src[i];
+    has[s] = 1;
+    finish[s] = std::max(finish[s], ap);
+    if (batch || (aq >= prm.warmup && aq < prm.cycles)) ej_req += pt.nfl[i];
+    if (batch || (ap >= prm.warmup && ap < prm.cycles)) ej_rep += pt.nfl[nq + i];
+    if (ti == ~0ull) continue;  // never issued: a deadlock ended the pass
+    flight += (double)(ap - ti);
+    if (!batch && tinj[i] < prm.warmup) continue;
+    ++r.measured;
+    lq += (double)(aq - ti);
+    lp += (double)(ap - (aq + prm.reply_delay));
+    lr += (double)(ap - ti);
+    stall += (double)(ti - tinj[i]);
+    r.max_round_trip_latency = std::max(r.max_round_trip_latency, (double)(ap - ti));
+    r.max_issue_stall = std::max(r.max_issue_stall, (double)(ti - tinj[i]));
+  }
+  if (r.measured) {
+    r.request_latency = lq / r.measured;
+    r.reply_latency = lp / r.measured;
+    r.round_trip_latency = lr / r.measured;
+    r.issue_stall = stall / r.measured;
+  }
+  r.batch_time = batch ? last : 0;
+  const double window = (batch ? (double)std::max<uint64_t>(last, 1) : (double)(prm.cycles - prm.warmup)) * N;
+  r.accepted_request = (double)ej_req / window;
+  r.accepted_reply = (double)ej_rep / window;
+  uint32_t active = 0;
+  bool first = true;
+  for (uint32_t s = 0; s < N; ++s) {
+    if (!has[s]) continue;
+    ++active;
+    r.first_finish = first ? finish[s] : std::min(r.first_finish, finish[s]);
+    r.last_finish = std::max(r.last_finish, finish[s]);
+    first = false;
+  }
+  r.avg_outstanding = active && last ? flight / ((double)active * (double)last) : 0;
+  const NetEnergy e = net_energy(net, pt.d, raw.pass.act, last);
+  r.e_buffer = e.buffer;
+  r.e_xbar = e.xbar;
+  r.e_link = e.link;
+  r.e_alloc = e.alloc;
+  r.e_leak = e.leak;
+  r.power_w = e.power_w;
+  if (arrivals) {
+    r.request_arrivals.assign(tarr.begin(), tarr.begin() + nq);
+    r.reply_arrivals.assign(tarr.begin() + nq, tarr.end());
+    r.tiss = std::move(raw.tiss);
+    r.state = std::move(raw.pass.state);
+    r.request_src = std::move(pt.req.src);
+    r.request_dst = std::move(pt.req.dst);
+    r.request_flits = std::move(pt.req.nfl);
+    r.request_tinj = std::move(pt.req.tinj);
+    r.kind = std::move(pt.kind);
+  }
+  return r;
+}
+
+}  // namespace
+
+std::vector<ClosedLoopResult> icnt_closed_loop_batch(const std::string& icnt_text,
+                                                     const std::vector<ClosedLoopParams>& points,
+                                                     const std::string& engine, const OpenLoopBatchOpts& opts) {
+  check_engine("icnt_closed_loop_batch", engine);
+  const OpenLoopNet net = icnt_open_loop_net(icnt_text);
+  const OpenLoopNet dbl = doubled_net(net);
+  std::vector<ClosedLoopResult> out;
+  out.reserve(points.size());
+  g_last = OpenLoopBatchStats();
+  if (engine != "gpu") {
+    for (size_t i = 0; i < points.size(); ++i) {
+      ClPoint pt = cl_prepare(net, dbl, points[i], i);
+      ClRaw raw = cl_host(dbl, pt, engine == "cpu-par", opts.step_cap);
+      out.push_back(cl_finish(net, pt, raw, opts.arrivals, i));
+    }
+    return out;
+  }
+  pack_chunks<ClPoint, ClRaw>(
+      "icnt_closed_loop_batch: point", opts, icnt_sweep_net_bytes(dbl), points.size(),
+      [&](size_t i) { return cl_prepare(net, dbl, points[i], i); },
+      [](const ClPoint& pt) { return icnt_cl_unit_bytes(cl_unit(pt)); },
+      [&](const std::vector<ClPoint>& chunk, std::vector<ClRaw>& raws) {
+        std::vector<ClUnit> units;
+        for (const ClPoint& pt : chunk) units.push_back(cl_unit(pt));
+        return icnt_cl_run_chunk(dbl, units, opts.step_cap, opts.lds, raws);
+      },
+      [&](ClPoint& pt, ClRaw& raw) { out.push_back(cl_finish(net, pt, raw, opts.arrivals, out.size())); });
   return out;
 }
 

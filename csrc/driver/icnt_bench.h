@@ -1,5 +1,5 @@
-// Open-loop synthetic traffic, packet-list replay and request-reply traffic
-// through the router model (icnt_bench.cc).
+// Open-loop synthetic traffic, packet-list replay, request-reply traffic and
+// closed-loop request-reply traffic through the router model (icnt_bench.cc).
 #pragma once
 #include <cstdint>
 #include <map>
@@ -196,5 +196,67 @@ std::vector<RequestReplyResult> icnt_request_reply_batch(const std::string& icnt
                                                          const std::vector<RequestReplyParams>& points,
                                                          const std::string& engine = "cpu",
                                                          const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
+
+// ---- closed-loop request-reply points: bounded windows (model/icnt_closed.h) ----
+
+// A node keeps at most `max_outstanding` requests in flight and issues the
+// next one when a reply has come back (Booksim's batchtrafficmanager.cpp:
+// sim_type = batch, batch_size, max_outstanding_requests).  Both subnets
+// advance on one clock: one router pass over the doubled network, two
+// disjoint copies of the .icnt file's network.  Differences from Booksim: a
+// node may issue several requests in one cycle, and a pending reply leaves
+// from the reply subnet's terminal instead of taking the node's injection
+// slot.  Two kinds of point:
+//   rate   (batch_size 0) the request list of a RequestReplyParams point with
+//          the same fields; with max_outstanding 0 the point is that point
+//   batch  every issuing node creates batch_size requests at cycle 0,
+//          destinations from the pattern, kinds from write_fraction
+struct ClosedLoopParams {
+  std::string traffic = "uniform";
+  uint64_t seed = 1;
+  double write_fraction = 0.5;
+  uint32_t read_request_size = 1, read_reply_size = 1, write_request_size = 1, write_reply_size = 1;  // flits
+  uint64_t reply_delay = 0;
+  uint32_t mem_nodes = 0;
+  uint32_t max_outstanding = 0;  // requests in flight per node, 0: unlimited
+  double rate = 0.1;             // rate points
+  uint64_t cycles = 2000, warmup = 500;
+  uint32_t batch_size = 0;   // > 0: a batch point
+  uint32_t batch_count = 1;  // only 1 is modelled
+};
+
+struct ClosedLoopResult {
+  uint32_t nodes = 0, issuers = 0;  // of one subnet; the nodes that hold requests
+  uint64_t requests = 0, measured = 0, reads = 0, writes = 0;
+  uint64_t batch_time = 0;  // the last reply's arrival (batch points; 0 otherwise)
+  // over the measured requests (rate points: created at or after warmup), from the issue time
+  double request_latency = 0, reply_latency = 0, round_trip_latency = 0, max_round_trip_latency = 0;
+  double issue_stall = 0, max_issue_stall = 0;  // issue - creation
+  // flits per node and cycle ejected on each subnet: in [warmup, cycles) for a
+  // rate point, over the batch time for a batch point
+  double accepted_request = 0, accepted_reply = 0;
+  double avg_outstanding = 0;  // requests in flight per issuing node, averaged over cycle 0 to the last reply
+  uint64_t first_finish = 0, last_finish = 0;  // the earliest and latest issuing node's last reply
+  uint32_t deadlocked = 0;
+  uint64_t activity[8] = {};  // both subnets (RtAct order)
+  double e_buffer = 0, e_xbar = 0, e_link = 0, e_alloc = 0, e_leak = 0, power_w = 0;
+  // on request (opts.arrivals): the request list, every request's issue time,
+  // both arrival arrays by request, the doubled network's state words
+  std::vector<uint32_t> request_src, request_dst, request_flits, kind;
+  std::vector<uint64_t> request_tinj, tiss, request_arrivals, reply_arrivals, state;
+};
+
+// every point through one engine: "cpu" (rt_simulate_closed), "cpu-par"
+// (rt_simulate_par_closed<SeqPar>) or "gpu" (engine/icnt_cl_sweep.hip, one
+// wavefront per point).  std::invalid_argument, naming the key: routing
+// functions min_adapt and valiant (their routes are no tables), batch_count
+// above 1, mem_nodes that leave no issuer, a network of more than
+// kClosedLoopMaxNodes nodes; std::runtime_error: a pass cut off by its loop
+// guard (opts.step_cap applies to every engine here).
+constexpr uint32_t kClosedLoopMaxNodes = 1024;
+std::vector<ClosedLoopResult> icnt_closed_loop_batch(const std::string& icnt_text,
+                                                     const std::vector<ClosedLoopParams>& points,
+                                                     const std::string& engine = "cpu",
+                                                     const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
 
 }  // namespace asim

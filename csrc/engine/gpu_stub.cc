@@ -56,4 +56,8 @@ bool icnt_net_run_chunk(const NetList&, const std::vector<NetUnit>&, uint64_t, b
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_net_kernel_info() { return {}; }
+bool icnt_cl_run_chunk(const OpenLoopNet&, const std::vector<ClUnit>&, uint64_t, bool, std::vector<ClRaw>&) {
+  throw std::runtime_error("no GPU engine in this build");
+}
+std::map<std::string, uint64_t> icnt_cl_kernel_info() { return {}; }
 }  // namespace asim

@@ -5,10 +5,11 @@
 // under a memory budget; one chunk is one launch.  A second kernel
 // (icnt_rr_sweep.hip) takes packet lists with per-packet sizes and
 // request-reply points, both subnets of a point in one wavefront; a third
-// (icnt_net_sweep.hip) one packet list over many networks.  What the three
+// (icnt_net_sweep.hip) one packet list over many networks; a fourth
+// (icnt_cl_sweep.hip) closed-loop points on the doubled network.  What the
 // launch paths share lives in two headers: icnt_sweep_layout.h (plain C++,
 // every build) has a chunk's layout, the descriptors and the `*_bytes` the
-// caller budgets with; icnt_sweep_dev.h (the three .hip files only) has the
+// caller budgets with; icnt_sweep_dev.h (the .hip files only) has the
 // pass with its LDS placement, the chunk's device block and the resource
 // query.  Host-only builds link the stub in gpu_stub.cc.
 #pragma once
@@ -106,5 +107,32 @@ bool icnt_net_run_chunk(const NetList& list, const std::vector<NetUnit>& units, 
                         std::vector<OpenLoopRaw>& raws);
 
 std::map<std::string, uint64_t> icnt_net_kernel_info();
+
+// ---- closed-loop points (icnt_cl_kernel, icnt_cl_sweep.hip) ----
+
+// one unit of a launch: a closed-loop point's 2 * nq packets on the doubled
+// network (requests, then their replies: model/icnt_closed.h) with the
+// requests' creation times
+struct ClUnit {
+  RtDims d{};  // the doubled network's pass
+  uint32_t nq = 0, window = 0;
+  uint64_t delay = 0;
+  const std::vector<uint32_t>*src = nullptr, *dst = nullptr, *nfl = nullptr;  // 2 * nq each
+  const std::vector<uint64_t>* tinj = nullptr;                               // nq
+};
+
+// what a unit leaves: the pass (tarr of the 2 * nq packets) and the issue times
+struct ClRaw {
+  OpenLoopRaw pass;
+  std::vector<uint64_t> tiss;
+};
+
+// one launch over the doubled network `net` (tables, `lat` / `inj_lat` empty
+// for the uniform channel latency): grid = the chunk's units, 64 lanes each.
+// Same LDS rule and return value as icnt_sweep_run_chunk.
+bool icnt_cl_run_chunk(const OpenLoopNet& net, const std::vector<ClUnit>& units, uint64_t step_cap, bool allow_lds,
+                       std::vector<ClRaw>& raws);
+
+std::map<std::string, uint64_t> icnt_cl_kernel_info();
 
 }  // namespace asim

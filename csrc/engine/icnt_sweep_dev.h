@@ -1,6 +1,6 @@
-// What the three network sweep kernels and their launch paths share
-// (icnt_sweep.hip, icnt_rr_sweep.hip, icnt_net_sweep.hip; included by those
-// three only): on the device the router pass of one unit with the placement
+// What the four network sweep kernels and their launch paths share
+// (icnt_sweep.hip, icnt_rr_sweep.hip, icnt_net_sweep.hip, icnt_cl_sweep.hip;
+// included by those four only): on the device the router pass of one unit with the placement
 // of its per-(unit, VC) words, on the host the chunk's device block with its
 // copies, and the kernels' resource query.  The chunk's layout is
 // icnt_sweep_layout.h.
@@ -37,6 +37,23 @@ __device__ __forceinline__ void sweep_pass(const SimCfg& c, const RtDims& d, uin
     lost = rt_simulate_par_hot<WavePar>(c, d, st, w, hv, np, o->act, &o->status, step_cap);
   } else {
     lost = rt_simulate_par<WavePar>(c, d, st, w, np, o->act, &o->status, step_cap);
+  }
+  WavePar::one([&] { o->deadlocked = lost; });
+}
+
+// The closed-loop pass of one unit (model/icnt_closed.h), same placement rule.
+__device__ __forceinline__ void sweep_pass_closed(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w,
+                                                  const RtClosed& cl, SweepOut* o, uint64_t step_cap, int hot_lds,
+                                                  uint32_t* hot_words) {
+  uint32_t lost = 0;
+  if (hot_lds) {
+    const uint32_t uv = d.U * d.V;
+    lds_u32* h = (lds_u32*)hot_words;
+    const RtHot<lds_u32*> hv{h, h + uv, h + 2 * uv, h + 3 * uv, h + 4 * uv};
+    lost = rt_simulate_par_closed<WavePar>(c, d, st, w, hv, cl, o->act, &o->status, step_cap);
+  } else {
+    const RtHot<uint32_t*> hv{w.vhead, w.vcnt, w.vown, w.vout, w.vocc};
+    lost = rt_simulate_par_closed<WavePar>(c, d, st, w, hv, cl, o->act, &o->status, step_cap);
   }
   WavePar::one([&] { o->deadlocked = lost; });
 }

@@ -66,11 +66,17 @@ struct alignas(16) NetPt {
   NetOff net;
   uint64_t st_off, scr_off;
 };
+struct alignas(16) ClPt {  // a closed-loop point on the doubled network
+  RtDims d;
+  uint32_t nq, window;
+  uint64_t delay;
+  uint64_t st_off, scr_off, cl_off;  // cl: rt_cl_carve(d, nq)
+};
 struct ListOff {  // the shared list of a many-networks chunk
   uint64_t src, dst, bytes, tinj;
 };
 static_assert(sizeof(SweepOut) % 16 == 0 && sizeof(SweepPt) % 16 == 0 && sizeof(RrPt) % 16 == 0 &&
-                  sizeof(NetPt) % 16 == 0,
+                  sizeof(NetPt) % 16 == 0 && sizeof(ClPt) % 16 == 0,
               "per-unit sums of the record arrays are exact");
 
 // ---- the fixed part of a chunk ----
@@ -134,6 +140,17 @@ inline NetPt place_net_unit(ChunkLayout& l, const NetUnit& u) {
   return h;
 }
 
+inline ClPt place_cl_unit(ChunkLayout& l, const ClUnit& u) {
+  ClPt h{};
+  h.d = u.d;
+  h.nq = u.nq;
+  h.window = u.window;
+  h.delay = u.delay;
+  place_pass(l, h.d, h.st_off, h.scr_off);
+  h.cl_off = l.take(rt_cl_carve(h.d, h.nq, nullptr, nullptr) * 4);
+  return h;
+}
+
 // ---- what the driver budgets with ----
 
 // device bytes of a chunk besides its units: the network of an open-loop or
@@ -161,6 +178,12 @@ inline uint64_t icnt_rr_unit_bytes(const RrUnit& u) {
   ChunkLayout l;
   l.records<RrPt>(1, 2);
   place_rr_unit(l, u);
+  return l.bytes;
+}
+inline uint64_t icnt_cl_unit_bytes(const ClUnit& u) {
+  ChunkLayout l;
+  l.records<ClPt>(1);
+  place_cl_unit(l, u);
   return l.bytes;
 }
 inline uint64_t icnt_net_unit_bytes(const NetUnit& u) {

@@ -1,0 +1,212 @@
+// Closed-loop request-reply traffic with bounded windows: the rules a router
+// pass needs on top of RtCtx (icnt_router.h, which includes this file after
+// RtCtx) when a request's delivery creates its reply and a reply's delivery
+// lets its node issue again.  Reference: intersim2/batchtrafficmanager.cpp
+// (sim_type = batch: batch_size, max_outstanding_requests).
+//
+// The pass runs over the doubled network: two disjoint copies of one network,
+// nodes [0, N) with links [0, L) the request subnet and nodes [N, 2N) with
+// links [L, 2L) the reply subnet, routes from tables (RtWork::rt_off).  It
+// holds 2 * nq packets:
+//   request i       src[i] -> dst[i]          i in [0, nq), time-ordered
+//   reply  nq + i   N + dst[i] -> N + src[i]  flits by the request's kind
+// A reply's source, destination and flits are known up front (rt_cl_fill_reply);
+// its injection time is not.
+//
+// Rules (one element each, like RtCtx's members; the drivers decide the order
+// and the parallelism):
+//  1. Issue gate (rt_cl_gate).  Node s issues its requests in list order.
+//     Request k is issued at the smallest cycle t >= max(tinj[k], tiss[k-1])
+//     at which fewer than `window` of the node's earlier requests are
+//     outstanding; a request is outstanding from its issue until the arrival
+//     of its reply's tail at s, and a reply arriving at t frees its slot for
+//     t.  window 0: unlimited.  From its issue on a request is an ordinary
+//     packet of its node's source queue with injection time tiss (w.tinj is
+//     overwritten: before the issue it holds the creation time).  Several
+//     requests of a node may issue in one cycle.  Booksim issues at most one
+//     packet per node and cycle and lets a pending reply take the node's
+//     injection slot; here the reply leaves from the other subnet's terminal.
+//  2. Reply creation (rt_cl_delivered, a request).  A request whose tail is
+//     delivered with arrival arr creates its reply with tinj = arr + delay at
+//     the tail of node N + dst's source queue.  Arrivals at a node come over
+//     its one ejection link and strictly increase, so the tail append keeps
+//     the queue in (time, packet) order.
+//  3. Release (rt_cl_delivered, a reply).  The reply's arrival is queued on
+//     its requester's release list, in time order for the same reason, and
+//     applied by the gate at the top of the cycle it falls due.
+//
+// The source list.  Open loop, a source is listed from the start, in the
+// order of the sources' first packets, until its queue runs empty for good.
+// The list's order decides the order of the active list and so of the request
+// list, which the maximum-size allocator depends on.  To give that order here,
+// a source is listed from its first packet (a request node at setup, a reply
+// node when its first reply is created: rt_cl_list_source inserts it by the
+// key (time, packet) of that packet) until it has injected the last packet it
+// will ever have (`left`), also while its queue is empty.  With an unlimited
+// window the pass then is, subnet by subnet, the open-loop request-reply pass
+// (for the allocators whose matching does not depend on unit indices, which
+// the doubled network renumbers -- not wavefront and PIM -- and for whole
+// internal speedups: a fractional one adds its extra pass per loop iteration,
+// and this pass iterates through the union of both subnets' busy cycles).
+//
+// Events: besides the sources', units' and credits' times the next-event scan
+// sees rt_cl_gate_time: the creation time of a node's next request while its
+// gate is open, its earliest queued release while it is closed.  These add at
+// most 2 * nq event times to a pass (rt_cl_step_cap).
+#pragma once
+
+namespace asim {
+
+// parameters and work arrays of a closed-loop pass; d.N is the doubled network's
+struct RtClosed {
+  uint32_t nq = 0;      // requests (the pass has 2 * nq packets)
+  uint32_t window = 0;  // outstanding requests per node, 0: unlimited
+  uint64_t delay = 0;   // request arrival to reply creation
+  uint64_t* tiss = nullptr;  // [nq] issue time, ~0: not issued
+  uint32_t *gnext = nullptr, *rnext = nullptr;  // [nq] a node's next request; its next queued release
+  // [d.N] next request to issue, last request (setup), release list, requests
+  // outstanding, packets still to inject, the first packet ever queued
+  uint32_t *ghead = nullptr, *gtail = nullptr, *rhead = nullptr, *rtail = nullptr, *out = nullptr, *left = nullptr,
+           *sfirst = nullptr;
+};
+
+// carve the closed-loop arrays out of `base` (nullptr: size only); u32 words
+SIM_HDI uint64_t rt_cl_carve(const RtDims& d, uint32_t nq, uint32_t* base, RtClosed* cl) {
+  uint64_t off = 0;
+  auto take32 = [&](uint64_t n) -> uint32_t* {
+    uint32_t* p = base ? base + off : nullptr;
+    off += n;
+    return p;
+  };
+  RtClosed t = cl ? *cl : RtClosed();
+  t.nq = nq;
+  t.tiss = reinterpret_cast<uint64_t*>(take32(2ull * nq));  // (base is 8-byte aligned)
+  t.gnext = take32(nq);
+  t.rnext = take32(nq);
+  t.ghead = take32(d.N);
+  t.gtail = take32(d.N);
+  t.rhead = take32(d.N);
+  t.rtail = take32(d.N);
+  t.out = take32(d.N);
+  t.left = take32(d.N);
+  t.sfirst = take32(d.N);
+  if (cl) *cl = t;
+  return (off + 1) & ~1ull;
+}
+
+SIM_HDI uint64_t rt_cl_step_cap(const RtDims& d, uint64_t flits, uint32_t nq) {
+  return rt_step_cap(d, flits) + kRtGuardFactor * 2ull * nq;
+}
+
+// reply nq + i of request i on an n-node network: src / dst / nfl of the pass
+SIM_HDI void rt_cl_fill_reply(uint32_t* src, uint32_t* dst, uint32_t* nfl, uint32_t nq, uint32_t i, uint32_t n,
+                              uint32_t write, uint32_t fl_read, uint32_t fl_write) {
+  src[nq + i] = n + dst[i];
+  dst[nq + i] = n + src[i];
+  nfl[nq + i] = write ? fl_write : fl_read;
+}
+
+// packet p to the tail of node s's source queue
+SIM_HDI void rt_cl_enqueue(const RtWork& w, uint32_t s, uint32_t p) {
+  if (w.shead[s] == kRtNone) w.shead[s] = p;
+  else w.next[w.stail[s]] = p;
+  w.stail[s] = p;
+}
+
+// setup, single-threaded, after init_packet of every packet: the nodes'
+// request lists and packet counts; the request nodes enter the source list
+// in the order of their first requests
+template <class CX>
+SIM_HDI void rt_cl_setup(const CX& cx, const RtClosed& cl, uint32_t& nsrc) {
+  const RtWork& w = cx.w;
+  for (uint32_t s = 0; s < cx.N; ++s) {
+    cl.ghead[s] = cl.gtail[s] = cl.rhead[s] = cl.rtail[s] = cl.sfirst[s] = kRtNone;
+    cl.out[s] = cl.left[s] = 0;
+  }
+  for (uint32_t i = 0; i < cl.nq; ++i) {
+    const uint32_t s = w.src[i];
+    cl.tiss[i] = ~0ull;
+    cl.gnext[i] = cl.rnext[i] = kRtNone;
+    if (cl.ghead[s] == kRtNone) {
+      cl.ghead[s] = cl.sfirst[s] = i;
+      w.sflag[s] = 1;
+      w.slist[nsrc++] = s;
+    } else {
+      cl.gnext[cl.gtail[s]] = i;
+    }
+    cl.gtail[s] = i;
+    ++cl.left[s];
+    ++cl.left[w.src[cl.nq + i]];
+  }
+}
+
+// rule 1 and the due part of rule 3 for node s at the top of cycle `now`
+template <class CX>
+SIM_HDI void rt_cl_gate(const CX& cx, const RtClosed& cl, uint32_t s, uint64_t now) {
+  const RtWork& w = cx.w;
+  for (uint32_t r; (r = cl.rhead[s]) != kRtNone && w.tarr[cl.nq + r] <= now;) {
+    --cl.out[s];
+    cl.rhead[s] = cl.rnext[r];
+  }
+  for (uint32_t p; (p = cl.ghead[s]) != kRtNone && w.tinj[p] <= now && (!cl.window || cl.out[s] < cl.window);) {
+    cl.tiss[p] = now;
+    w.tinj[p] = now;
+    ++cl.out[s];
+    cl.ghead[s] = cl.gnext[p];
+    rt_cl_enqueue(w, s, p);
+  }
+}
+
+// the next time node s's gate can do anything (~0: never without another event)
+template <class CX>
+SIM_HDI uint64_t rt_cl_gate_time(const CX& cx, const RtClosed& cl, uint32_t s) {
+  const uint32_t p = cl.ghead[s];
+  if (p == kRtNone) return ~0ull;
+  if (!cl.window || cl.out[s] < cl.window) return cx.w.tinj[p];
+  const uint32_t r = cl.rhead[s];
+  return r == kRtNone ? ~0ull : cx.w.tarr[cl.nq + r];
+}
+
+// a listed source s stays listed while it has packets to inject, queued or not
+SIM_HDI bool rt_cl_listed(const RtClosed& cl, uint32_t s) { return cl.left[s] != 0; }
+// source s injected the last flit of a packet
+SIM_HDI void rt_cl_injected(const RtClosed& cl, uint32_t s) { --cl.left[s]; }
+
+// rules 2 and 3: the tail of packet p was delivered (w.tarr[p] is set).
+// Returns the reply node that queued its first packet and is to be listed
+// (rt_cl_list_source), else kRtNone.  Two packets delivered in one switch pass
+// arrive at different nodes, so they touch different queues and lists.
+template <class CX>
+SIM_HDI uint32_t rt_cl_delivered(const CX& cx, const RtClosed& cl, uint32_t p) {
+  const RtWork& w = cx.w;
+  if (p < cl.nq) {
+    const uint32_t q = cl.nq + p, n = w.src[q];
+    w.tinj[q] = w.tarr[p] + cl.delay;
+    rt_cl_enqueue(w, n, q);
+    if (cl.sfirst[n] != kRtNone) return kRtNone;
+    cl.sfirst[n] = q;
+    return n;
+  }
+  const uint32_t i = p - cl.nq, s = w.src[i];
+  if (cl.rhead[s] == kRtNone) cl.rhead[s] = i;
+  else cl.rnext[cl.rtail[s]] = i;
+  cl.rtail[s] = i;
+  return kRtNone;
+}
+
+// list source n by the (time, packet) key of its first packet; single-threaded
+template <class CX>
+SIM_HDI void rt_cl_list_source(const CX& cx, const RtClosed& cl, uint32_t n, uint32_t& nsrc) {
+  const RtWork& w = cx.w;
+  const uint32_t fp = cl.sfirst[n];
+  uint32_t i = nsrc++;
+  for (; i > 0; --i) {
+    const uint32_t o = cl.sfirst[w.slist[i - 1]];
+    if (w.tinj[o] < w.tinj[fp] || (w.tinj[o] == w.tinj[fp] && o < fp)) break;
+    w.slist[i] = w.slist[i - 1];
+  }
+  w.slist[i] = n;
+  w.sflag[n] = 1;
+}
+
+}  // namespace asim

@@ -713,6 +713,27 @@ struct RtCtx {
   }
 };
 
+// ---- the loop guard ----
+// Every iteration of a pass's main loop either moves something (a credit, an
+// injected flit, a flit hop) or jumps to a later event time, and there are at
+// most as many distinct event times as events.  With E = flit-hops + credits
+// + injections <= 2 * flits * H + flits, the loop is cut off after
+// kRtGuardFactor * E + U + 64 iterations (a factor 2 would do for a correct
+// pass; 4 leaves a margin) and the pass reports RT_STATUS_STEP_CAP: a bug ends
+// the pass instead of spinning it.
+enum RtStatus : uint32_t { RT_STATUS_OK = 0, RT_STATUS_STEP_CAP = 1 };
+constexpr uint64_t kRtGuardFactor = 4;
+
+SIM_HDI uint64_t rt_step_cap(const RtDims& d, uint64_t flits) {
+  return kRtGuardFactor * (2 * flits * d.H + flits) + d.U + 64;
+}
+
+}  // namespace asim
+
+#include "icnt_closed.h"  // the closed-loop rules (RtClosed, rt_cl_*)
+
+namespace asim {
+
 // ---- the serial driver ----
 // Simulate the `np` packets already in w (src, dst, nfl, tinj) through one
 // subnet whose persistent state is `st` (rt_state_words); fills w.tarr (the
@@ -720,8 +741,15 @@ struct RtCtx {
 // could not be delivered (a routing deadlock: they get their uncontended
 // traversal after the last delivery).  Single-threaded: plain loops over the
 // source list, the active list, the request list and the credit FIFO.
-SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, uint32_t np,
-                             uint64_t* act = nullptr) {
+//
+// Closed (compile time; rt_simulate_closed): the closed-loop pass of
+// icnt_closed.h over the doubled network, np = 2 * cl.nq.  The source queues
+// start empty and fill from the nodes' issue gates and the requests'
+// deliveries; the loop guard of the lane-parallel pass is in force (status,
+// step_cap 0: rt_cl_step_cap).  Open loop none of this is compiled.
+template <bool Closed>
+SIM_HDI uint32_t rt_simulate_core(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, uint32_t np,
+                                  uint64_t* act, const RtClosed& cl, uint32_t* status, uint64_t step_cap) {
   const RtCtx<RtHot<uint32_t*>> cx(c, d, st, w, RtHot<uint32_t*>{w.vhead, w.vcnt, w.vown, w.vout, w.vocc});
   const RtHot<uint32_t*>& hv = cx.hv;  // the hot words: the driver and RtCtx go through the same view
   const uint32_t V = cx.V, B = cx.B, N = cx.N, L = cx.L, U = cx.U;
@@ -738,8 +766,9 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
     w.fbase[p] = nf;
     cx.init_packet(p, nf);
     nf += w.nfl[p];
-    cx.link_source(p, nsrc);
+    if constexpr (!Closed) cx.link_source(p, nsrc);
   }
+  if constexpr (Closed) rt_cl_setup(cx, cl, nsrc);
   for (uint64_t i = 0; i < (uint64_t)U * V; ++i) {
     hv.vhead[i] = hv.vcnt[i] = hv.vocc[i] = 0;
     hv.vown[i] = hv.vout[i] = kRtNone;
@@ -759,10 +788,18 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
   };
   uint64_t now = ~0ull;
   for (uint32_t i = 0; i < nsrc; ++i) {
-    const uint64_t t = cx.source_time(w.slist[i]);
+    uint64_t t = cx.source_time(w.slist[i]);
+    if constexpr (Closed) t = rt_cl_gate_time(cx, cl, w.slist[i]);
     if (t < now) now = t;
   }
+  uint64_t steps = 0;
   while (remaining > 0) {
+    if constexpr (Closed) {
+      if (++steps > (step_cap ? step_cap : rt_cl_step_cap(d, nf, cl.nq))) {
+        *status = RT_STATUS_STEP_CAP;
+        return remaining;
+      }
+    }
     bool progress = false;
     // ---- credits that reach their upstream this cycle ----
     while (cr_r < cr_w && w.crt[cr_r] <= now) {
@@ -776,12 +813,14 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       uint32_t keep = 0;
       for (uint32_t i = 0; i < nsrc; ++i) {
         const uint32_t s = w.slist[i];
+        if constexpr (Closed) rt_cl_gate(cx, cl, s, now);
         const uint32_t p = w.shead[s];
-        if (p == kRtNone) {
+        if (Closed ? !rt_cl_listed(cl, s) : p == kRtNone) {
           w.sflag[s] = 0;
           continue;
         }
         w.slist[keep++] = s;
+        if (Closed && p == kRtNone) continue;
         if (now < w.tinj[p] || now < inj_next[s]) continue;
         if (w.svc[s] == kRtNone) {
           const uint32_t v = cx.free_vc(s, 2);
@@ -805,6 +844,7 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
           w.sfl[s] = 0;
           w.svc[s] = kRtNone;
           w.shead[s] = w.next[p];
+          if constexpr (Closed) rt_cl_injected(cl, s);
         }
       }
       nsrc = keep;
@@ -915,6 +955,10 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
             activate(N + l);
           } else if (hop.to == kRtDelivered) {
             --remaining;
+            if constexpr (Closed) {
+              const uint32_t n = rt_cl_delivered(cx, cl, w.fpk[hop.f]);
+              if (n != kRtNone) rt_cl_list_source(cx, cl, n, nsrc);
+            }
           }
         }
         if (!any) break;
@@ -945,6 +989,10 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
       for (uint32_t i = 0; i < nsrc; ++i) {
         const uint64_t t = cx.source_time(w.slist[i]);
         if (t > now && t < nxt) nxt = t;  // (t <= now: waiting for a credit)
+        if constexpr (Closed) {
+          const uint64_t g = rt_cl_gate_time(cx, cl, w.slist[i]);
+          if (g > now && g < nxt) nxt = g;
+        }
       }
       for (uint32_t i = 0; i < nact; ++i) {
         const uint64_t t = cx.unit_time(w.act[i], now);
@@ -957,6 +1005,19 @@ SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, con
   if (remaining)
     for (uint32_t p = 0; p < np; ++p) cx.deadlock_arrival(p, now);
   return remaining;
+}
+
+SIM_HDN uint32_t rt_simulate(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, uint32_t np,
+                             uint64_t* act = nullptr) {
+  return rt_simulate_core<false>(c, d, st, w, np, act, RtClosed(), nullptr, 0);
+}
+
+// the closed-loop pass (icnt_closed.h); *status: RT_STATUS_*, after
+// RT_STATUS_STEP_CAP nothing of the pass is valid
+SIM_HDN uint32_t rt_simulate_closed(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w,
+                                    const RtClosed& cl, uint64_t* act, uint32_t* status, uint64_t step_cap) {
+  *status = RT_STATUS_OK;
+  return rt_simulate_core<true>(c, d, st, w, 2 * cl.nq, act, cl, status, step_cap);
 }
 
 // ---- injection back-pressure (-icnt_link_contention 2) ----

@@ -54,13 +54,16 @@
 //                   (augmenting paths), PIM (a reservoir over the requesters
 //                   in list order) and LOA (RtCtx::allocate_ordered)
 //
-// Loop guard: every iteration of the main loop either moves something (a
-// credit, an injected flit, a flit hop) or jumps to a later event time, and
-// there are at most as many distinct event times as events.  With
-// E = flit-hops + credits + injections <= 2 * flits * H + flits, the loop is
-// cut off after kRtGuardFactor * E + U + 64 iterations (a factor 2 would do
-// for a correct pass; 4 leaves a margin) and the pass reports
+// Loop guard: rt_step_cap (icnt_router.h); a pass that exceeds it reports
 // RT_STATUS_STEP_CAP: a bug ends the pass instead of spinning it.
+//
+// Closed loop (icnt_closed.h; rt_simulate_par_closed): the same driver with
+// the closed-loop rules compiled in.  The issue gate runs a lane per listed
+// source at the top of the injection phase; reply creation and release
+// queuing run a lane per delivered packet in commit step 1 (two packets
+// delivered in one switch pass arrive at different nodes); a reply node's
+// first listing is an insertion by key under P::one, at most once per node
+// and pass.
 //
 // Users: the open-loop sweep kernel (engine/icnt_sweep.hip, one wavefront per
 // network) and, under -sim_router_pass par, the cycle engines' epoch pass
@@ -70,17 +73,12 @@
 
 namespace asim {
 
-enum RtStatus : uint32_t { RT_STATUS_OK = 0, RT_STATUS_STEP_CAP = 1 };
-constexpr uint64_t kRtGuardFactor = 4;
-
-SIM_HDI uint64_t rt_step_cap(const RtDims& d, uint64_t flits) {
-  return kRtGuardFactor * (2 * flits * d.H + flits) + d.U + 64;
-}
-
 // status (when given): RT_STATUS_*; step_cap 0: rt_step_cap of the pass
-template <class P, class HV>
-SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, const HV& hv,
-                                     uint32_t np, uint64_t* act, uint32_t* status, uint64_t step_cap) {
+// (Closed: rt_cl_step_cap)
+template <class P, class HV, bool Closed>
+SIM_HDI uint32_t rt_simulate_par_core(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, const HV& hv,
+                                      uint32_t np, uint64_t* act, uint32_t* status, uint64_t step_cap,
+                                      const RtClosed& cl) {
   const RtCtx<HV> cx(c, d, st, w, hv);
   const uint32_t V = cx.V, B = cx.B, N = cx.N, L = cx.L, U = cx.U, alloc = cx.alloc;
   uint64_t *const gptr = cx.gptr, *const in_free = cx.in_free, *const aptr = cx.aptr, *const inj_next = cx.inj_next;
@@ -108,7 +106,9 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
   // source queues (injection order: time, then packet)
   uint32_t nsrc = 0;
   P::one([&] {
-    for (uint32_t p = 0; p < np; ++p) cx.link_source(p, nsrc);
+    if constexpr (Closed) rt_cl_setup(cx, cl, nsrc);
+    else
+      for (uint32_t p = 0; p < np; ++p) cx.link_source(p, nsrc);
   });
   nsrc = P::uni(nsrc);
   P::sync();
@@ -118,12 +118,13 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
   {
     uint64_t m = ~0ull;
     P::lane_loop((int)nsrc, [&](int i) {
-      const uint64_t t = cx.source_time(w.slist[i]);
+      uint64_t t = cx.source_time(w.slist[i]);
+      if constexpr (Closed) t = rt_cl_gate_time(cx, cl, w.slist[i]);
       if (t < m) m = t;
     });
     now = P::red_min64(m);
   }
-  const uint64_t cap = step_cap ? step_cap : rt_step_cap(d, nf);
+  const uint64_t cap = step_cap ? step_cap : Closed ? rt_cl_step_cap(d, nf, cl.nq) : rt_step_cap(d, nf);
   uint64_t steps = 0;
   uint32_t stat = RT_STATUS_OK;
   // rq_o[j] of a request that was not committed: else RtHop::to of its traversal
@@ -159,16 +160,18 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
     {
       P::each((int)nsrc, [&](int i) {
         const uint32_t s = w.slist[i];
+        if constexpr (Closed) rt_cl_gate(cx, cl, s, now);
         const uint32_t p = w.shead[s];
         uint32_t fl = 0;  // 1 stays listed, 2 input unit newly active, 4 injected
         w.st_u[i] = s;
-        if (p == kRtNone) {
+        if (Closed ? !rt_cl_listed(cl, s) : p == kRtNone) {
           w.sflag[s] = 0;
           w.gb[i] = 0;
           return;
         }
         fl = 1;
         w.gb[i] = fl;
+        if (Closed && p == kRtNone) return;
         if (now < w.tinj[p] || now < inj_next[s]) return;
         if (w.svc[s] == kRtNone) {
           const uint32_t v = cx.free_vc(s, 2);
@@ -194,6 +197,7 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
           w.sfl[s] = 0;
           w.svc[s] = kRtNone;
           w.shead[s] = w.next[p];
+          if constexpr (Closed) rt_cl_injected(cl, s);
         }
         w.gb[i] = fl;
       });
@@ -345,8 +349,25 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
           const RtHop hop = cx.traverse(w.rq_u[j], w.rq_l[j], rtag, alloc != RT_ISLIP || it == 0, now, cr_w + x);
           w.rq_k[j] = hop.f;
           w.rq_o[j] = hop.to;
+          // closed loop: the delivered packet's reply or release; rq_k (which
+          // step 2 needs of moved flits only) then names a reply node to list
+          if constexpr (Closed)
+            if (hop.to == kRtDelivered) w.rq_k[j] = rt_cl_delivered(cx, cl, w.fpk[hop.f]);
         });
         P::sync();
+        if constexpr (Closed) {
+          auto lists = [&](int j) { return w.rq_o[j] == kRtDelivered && w.rq_k[j] != kRtNone; };
+          const uint32_t nnew = P::sum((int)nrq, [&](int j) { return lists(j) ? 1u : 0u; });
+          if (nnew) {
+            P::one([&] {
+              uint32_t ns = nsrc;
+              for (uint32_t j = 0; j < nrq; ++j)
+                if (lists((int)j)) rt_cl_list_source(cx, cl, w.rq_k[j], ns);
+            });
+            nsrc += nnew;
+            P::sync();
+          }
+        }
         // step 2: the pushes; newly active downstream units in request order
         P::each((int)nrq, [&](int j) {
           const uint32_t duv = w.rq_o[j];
@@ -401,6 +422,10 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
       P::lane_loop((int)nsrc, [&](int i) {
         const uint64_t t = cx.source_time(w.slist[i]);
         if (t > now && t < m) m = t;  // (t <= now: waiting for a credit)
+        if constexpr (Closed) {
+          const uint64_t g = rt_cl_gate_time(cx, cl, w.slist[i]);
+          if (g > now && g < m) m = g;
+        }
       });
       P::lane_loop((int)nact, [&](int i) {
         const uint64_t t = cx.unit_time(w.act[i], now);
@@ -421,6 +446,20 @@ SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t*
   });
   P::sync();
   return remaining;
+}
+
+template <class P, class HV>
+SIM_HDN uint32_t rt_simulate_par_hot(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, const HV& hv,
+                                     uint32_t np, uint64_t* act, uint32_t* status, uint64_t step_cap) {
+  return rt_simulate_par_core<P, HV, false>(c, d, st, w, hv, np, act, status, step_cap, RtClosed());
+}
+
+// the closed-loop pass of icnt_closed.h over the doubled network (2 * cl.nq
+// packets); bit for bit rt_simulate_closed
+template <class P, class HV>
+SIM_HDN uint32_t rt_simulate_par_closed(const SimCfg& c, const RtDims& d, uint64_t* st, const RtWork& w, const HV& hv,
+                                        const RtClosed& cl, uint64_t* act, uint32_t* status, uint64_t step_cap) {
+  return rt_simulate_par_core<P, HV, true>(c, d, st, w, hv, 2 * cl.nq, act, status, step_cap, cl);
 }
 
 template <class P>
