@@ -44,8 +44,18 @@ window.  The ``.icnt`` keys ``max_outstanding_requests`` and ``batch_size``
 are the defaults, the latter when ``sim_type = batch``.  Unlike Booksim a
 node may issue several requests in one cycle, and a reply leaves from the
 reply subnet's terminal instead of taking its node's injection slot.
-Closed-loop replay of capture files is not offered: a capture does not pair
-replies with requests.
+
+``--closed-loop --replay FILE [--networks a.icnt,b.icnt,...]`` runs the
+requests of a capture file (or of an ``.npz`` with ``src``, ``dst``,
+``bytes``, ``reply_bytes``, ``tinj``) closed loop on every network of the
+list under every window of ``--max-outstanding``: each reply is created by
+its request's delivery on that network, with the size the capture recorded
+(icnt/capture.py ``request_list`` pairs them per cluster, sub-partition and
+kind), so the batch time is the time the application's own requests take on
+that network when a node may keep M in flight.  ``--timing batch`` makes
+every request ready at cycle 0, in captured order, in place of the captured
+creation times.  ``--engine gpu``: one wavefront per (network, window) in one
+launch (csrc/engine/icnt_cln_sweep.hip).
 """
 from __future__ import annotations
 
@@ -274,6 +284,80 @@ def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = Non
     return curve
 
 
+def _print_closed_loop(c: Dict, batch: bool) -> None:
+    if batch:
+        print(f"Batch received. Time used is {c['batch_time']:.0f} cycles "
+              f"(nodes finish between {c['first_finish']:.0f} and {c['last_finish']:.0f})")
+    print(f"Request average latency = {c['request_latency']:.2f}, reply average latency = {c['reply_latency']:.2f}")
+    print(f"Round-trip average latency = {c['round_trip_latency']:.2f} (max {c['max_round_trip_latency']:.0f}), "
+          f"from the issue")
+    print(f"Issue stall = {c['issue_stall']:.2f} cycles (max {c['max_issue_stall']:.0f}); "
+          f"outstanding requests per node = {c['avg_outstanding']:.2f}")
+    print(f"Accepted rate: request {c['accepted_request']:.4f}, reply {c['accepted_reply']:.4f}")
+
+
+def closed_loop_replay(src, dst, req_bytes, reply_bytes, tcreate, icnt_texts: List[str],
+                       max_outstanding: Optional[List[int]] = None, reply_delay: int = 0, engine: str = "cpu",
+                       arrivals: bool = False, mem_budget_mb: int = 0, lds: bool = True,
+                       nodes: int = 0) -> List[Dict]:
+    """One request list, closed loop, through many networks under many windows:
+    one dict per (``.icnt`` text, window of `max_outstanding`), network-major,
+    with its ``network`` index and ``max_outstanding``.  Request i goes from
+    ``src[i]`` to ``dst[i]`` with ``req_bytes[i]`` bytes, is created at
+    ``tcreate[i]`` (non-decreasing) and is answered, `reply_delay` cycles
+    after its delivery, by ``reply_bytes[i]`` bytes; every network derives its
+    own flit counts from the bytes, and a node keeps at most M requests in
+    flight (0, the default: unlimited).  ``batch_time`` is the last reply's
+    arrival.  The list of a capture file: ``capture.request_list``.
+    ``engine="gpu"`` runs one wavefront per (network, window), as many per
+    launch as the memory budget takes (csrc/engine/icnt_cln_sweep.hip).
+    `nodes`: the list's node count; a network with another one is refused (0:
+    not checked)."""
+    mod = _native.load(prefer_torch_runtime=engine == "gpu")
+    windows = [0] if max_outstanding is None else [int(m) for m in max_outstanding]
+    return [dict(d) for d in mod.icnt_closed_loop_networks(
+        (src, dst, req_bytes, reply_bytes, tcreate), list(icnt_texts), windows, reply_delay=int(reply_delay),
+        engine=engine, arrivals=arrivals, mem_budget_mb=mem_budget_mb, lds=lds, nodes=nodes)]
+
+
+def _main_closed_replay(a) -> int:
+    import numpy as np
+    from . import capture
+    if capture.is_capture(a.replay):
+        rl = capture.request_list(capture.load(a.replay), timing=a.timing)
+        lst, nodes = (rl.src, rl.dst, rl.req_bytes, rl.reply_bytes, rl.tcreate), rl.nodes
+    else:
+        with np.load(a.replay) as z:
+            missing = [k for k in ("src", "dst", "bytes", "reply_bytes", "tinj") if k not in z]
+            if missing:
+                print(f"--closed-loop --replay needs a request list with reply sizes: {a.replay} has no "
+                      f"{', '.join(missing)} (a capture file, or an .npz with src, dst, bytes, reply_bytes and tinj: "
+                      f"capture.save_request_npz)", file=sys.stderr)
+                return 2
+            order = np.argsort(z["tinj"], kind="stable")
+            tinj = z["tinj"][order].astype(np.uint64)
+            lst = (z["src"][order], z["dst"][order], z["bytes"][order], z["reply_bytes"][order],
+                   tinj if a.timing == "captured" else np.zeros_like(tinj))
+            nodes = int(z["nodes"]) if "nodes" in z else 0
+    files = [n for n in (a.networks or "").split(",") if n] or [a.config]
+    windows = [int(x) for x in a.max_outstanding.split(",") if x] if a.max_outstanding else [0]
+    res = closed_loop_replay(*lst, [open(f).read() for f in files], windows, reply_delay=a.reply_delay,
+                             engine=a.engine, mem_budget_mb=a.mem_budget_mb, nodes=nodes)
+    for c in res:
+        m = c["max_outstanding"]
+        c["config"] = files[c["network"]]
+        print(f"====== Closed-loop replay of {a.replay} on {c['config']}, {a.timing} timing, "
+              f"max outstanding {m if m else 'unlimited'} ======")
+        _print_closed_loop(c, True)
+        print(f"Packets = {c['requests']} requests ({c['request_flits']} flits), {c['reply_flits']} reply flits"
+              + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump({"replay": a.replay, "closed_loop": True, "timing": a.timing, "reply_delay": a.reply_delay,
+                       "networks": files, "max_outstanding": windows, "grid": res}, f, indent=1)
+    return 0
+
+
 def _main_closed_loop(a, text: str) -> int:
     traffics = [t for t in a.traffic.split(",") if t]
     seeds = list(range(1, a.seeds + 1)) if a.seeds > 0 else None
@@ -295,15 +379,7 @@ def _main_closed_loop(a, text: str) -> int:
         m = c["max_outstanding"]
         what = f"batch size {batch}" if batch is not None else f"injection rate {c['rate']:.3f}"
         print(f"====== Traffic {c['traffic']}, closed loop, {what}, max outstanding {m if m else 'unlimited'} ======")
-        if batch is not None:
-            print(f"Batch received. Time used is {c['batch_time']:.0f} cycles "
-                  f"(nodes finish between {c['first_finish']:.0f} and {c['last_finish']:.0f})")
-        print(f"Request average latency = {c['request_latency']:.2f}, reply average latency = {c['reply_latency']:.2f}")
-        print(f"Round-trip average latency = {c['round_trip_latency']:.2f} (max {c['max_round_trip_latency']:.0f}), "
-              f"from the issue")
-        print(f"Issue stall = {c['issue_stall']:.2f} cycles (max {c['max_issue_stall']:.0f}); "
-              f"outstanding requests per node = {c['avg_outstanding']:.2f}")
-        print(f"Accepted rate: request {c['accepted_request']:.4f}, reply {c['accepted_reply']:.4f}")
+        _print_closed_loop(c, batch is not None)
         print(f"Packets = {c['reads']} reads, {c['writes']} writes"
               + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
     if a.json:
@@ -448,17 +524,18 @@ def main(argv=None) -> int:
     ap.add_argument("--networks", metavar="A.icnt,B.icnt,...",
                     help="--replay: the list through each of these networks (in place of the one config), every "
                          "network with its own flit counts from the packets' bytes; --engine gpu: one launch")
+    ap.add_argument("--timing", choices=("captured", "batch"), default="captured",
+                    help="--closed-loop --replay: the requests' creation times as captured, or all at cycle 0 in "
+                         "captured order")
     ap.add_argument("--json", help="write the latency / throughput curve here")
     a = ap.parse_args(argv)
     a.rates_given = a.rates is not None
     if a.rates is None:
         a.rates = "0.05,0.1,0.2,0.3,0.4,0.5,0.6,0.8,1.0"
-    if a.closed_loop and a.replay:
-        ap.error("--closed-loop cannot replay a packet list: it does not pair replies with requests")
     if a.replay:
         if not a.config and not a.networks:
             ap.error("--replay needs a config or --networks")
-        return _main_replay(a)
+        return _main_closed_replay(a) if a.closed_loop else _main_replay(a)
     if not a.config:
         ap.error("the following arguments are required: config")
     if a.networks:

@@ -45,7 +45,8 @@ CORE_SRC = [
 HIP_SRC = ["csrc/engine/gpu_engine.hip", "csrc/engine/engine_k_lds.hip", "csrc/engine/engine_k_prof.hip",
            "csrc/engine/engine_k_global.hip", "csrc/engine/engine_k_split.hip", "csrc/engine/engine_k_split2.hip", "csrc/engine/ingest_mfma.hip",
            "csrc/engine/lane_check.hip", "csrc/engine/icnt_sweep.hip", "csrc/engine/icnt_rr_sweep.hip",
-           "csrc/engine/icnt_net_sweep.hip", "csrc/engine/icnt_cl_sweep.hip"]
+           "csrc/engine/icnt_net_sweep.hip", "csrc/engine/icnt_cl_sweep.hip",
+           "csrc/engine/icnt_cln_sweep.hip"]
 STUB_SRC = ["csrc/engine/gpu_stub.cc"]
 
 

@@ -663,6 +663,106 @@ PYBIND11_MODULE(_asim, m) {
       "issuer; step_cap is for tests and applies to every engine");
   m.def("icnt_cl_kernel_info", &icnt_cl_kernel_info, "registers, LDS and scratch of the closed-loop kernel");
   m.def(
+      "icnt_closed_loop_networks",
+      [](const py::tuple& list, const std::vector<std::string>& icnt_texts, const std::vector<uint32_t>& windows,
+         uint64_t reply_delay, const std::string& engine, bool arrivals, uint64_t mem_budget_mb, uint64_t step_cap,
+         bool lds, uint32_t nodes) {
+        typedef py::array_t<uint32_t, py::array::c_style | py::array::forcecast> A32;
+        typedef py::array_t<uint64_t, py::array::c_style | py::array::forcecast> A64;
+        if (list.size() != 5)
+          throw std::invalid_argument("icnt_closed_loop_networks: expected (src, dst, req_bytes, reply_bytes, tcreate)");
+        const A32 s = A32::ensure(list[0]), d = A32::ensure(list[1]), q = A32::ensure(list[2]), p = A32::ensure(list[3]);
+        const A64 tc = A64::ensure(list[4]);
+        if (!s || !d || !q || !p || !tc || s.ndim() != 1 || d.ndim() != 1 || q.ndim() != 1 || p.ndim() != 1 ||
+            tc.ndim() != 1)
+          throw std::invalid_argument("icnt_closed_loop_networks: src, dst, req_bytes, reply_bytes and tcreate must be "
+                                      "one-dimensional integer arrays");
+        ClosedLoopList l;
+        l.nodes = nodes;
+        // (an oversized list is refused by the call, before anything is simulated)
+        const size_t cap = (size_t)(kReplayMaxPackets / 2 + 1);
+        l.src.assign(s.data(), s.data() + std::min(cap, (size_t)s.size()));
+        l.dst.assign(d.data(), d.data() + std::min(cap, (size_t)d.size()));
+        l.req_bytes.assign(q.data(), q.data() + std::min(cap, (size_t)q.size()));
+        l.reply_bytes.assign(p.data(), p.data() + std::min(cap, (size_t)p.size()));
+        l.tcreate.assign(tc.data(), tc.data() + std::min(cap, (size_t)tc.size()));
+        OpenLoopBatchOpts o;
+        o.arrivals = arrivals;
+        o.mem_budget_mb = mem_budget_mb;
+        o.step_cap = step_cap;
+        o.lds = lds;
+        std::vector<ClosedLoopNetResult> rs;
+        {
+          py::gil_scoped_release nogil;
+          rs = icnt_closed_loop_networks(l, icnt_texts, windows, reply_delay, engine, o);
+        }
+        auto a32 = [](const std::vector<uint32_t>& v) { return py::array_t<uint32_t>((py::ssize_t)v.size(), v.data()); };
+        auto a64 = [](const std::vector<uint64_t>& v) { return py::array_t<uint64_t>((py::ssize_t)v.size(), v.data()); };
+        const char* an[] = {"buffer_writes", "buffer_reads", "link_flits", "eject_flits", "sa_requests", "credits",
+                            "switch_passes"};
+        py::list out;
+        for (const ClosedLoopNetResult& r : rs) {
+          py::dict dd;
+          dd["network"] = r.network;
+          dd["max_outstanding"] = r.window;
+          dd["nodes"] = r.nodes;
+          dd["issuers"] = r.issuers;
+          dd["requests"] = r.requests;
+          dd["measured_requests"] = r.measured;
+          dd["request_flits"] = r.request_flits;
+          dd["reply_flits"] = r.reply_flits;
+          dd["batch_time"] = r.batch_time;
+          dd["request_latency"] = r.request_latency;
+          dd["reply_latency"] = r.reply_latency;
+          dd["round_trip_latency"] = r.round_trip_latency;
+          dd["max_round_trip_latency"] = r.max_round_trip_latency;
+          dd["issue_stall"] = r.issue_stall;
+          dd["max_issue_stall"] = r.max_issue_stall;
+          dd["accepted_request"] = r.accepted_request;
+          dd["accepted_reply"] = r.accepted_reply;
+          dd["avg_outstanding"] = r.avg_outstanding;
+          dd["first_finish"] = r.first_finish;
+          dd["last_finish"] = r.last_finish;
+          dd["deadlocked"] = r.deadlocked;
+          py::dict a;
+          for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
+          dd["activity"] = a;
+          py::dict e;
+          e["buffer"] = r.e_buffer;
+          e["crossbar"] = r.e_xbar;
+          e["link"] = r.e_link;
+          e["allocator"] = r.e_alloc;
+          e["leakage"] = r.e_leak;
+          dd["energy_pj"] = e;
+          dd["power_w"] = r.power_w;
+          if (arrivals) {
+            dd["request_flit_counts"] = a32(r.request_flit_counts);
+            dd["reply_flit_counts"] = a32(r.reply_flit_counts);
+            dd["tiss"] = a64(r.tiss);
+            dd["request_arrivals"] = a64(r.request_arrivals);
+            dd["reply_arrivals"] = a64(r.reply_arrivals);
+            dd["state"] = a64(r.state);
+          }
+          out.append(dd);
+        }
+        return out;
+      },
+      py::arg("list"), py::arg("icnt_texts"), py::arg("windows"), py::arg("reply_delay") = 0, py::arg("engine") = "cpu",
+      py::arg("arrivals") = false, py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true,
+      py::kw_only(), py::arg("nodes") = 0,
+      "one request list (src, dst, req_bytes, reply_bytes, tcreate; tcreate non-decreasing) closed loop through many "
+      "networks under many windows, one result per (.icnt text, window), network-major: every network derives both "
+      "packets' flit counts from the bytes, a request's delivery creates its reply reply_delay cycles later and a "
+      "node keeps at most `window` requests in flight (0: unlimited).  batch_time is the last reply's arrival.  "
+      "nodes: the list's node count (0: not checked).  engine gpu: one wavefront per (network, window) in one launch "
+      "(icnt_cln_sweep.hip).  arrivals=True adds tiss, request_arrivals, reply_arrivals, the network's flit counts "
+      "and the state words.  ValueError names the network of a bad entry; step_cap is for tests");
+  m.def("icnt_closed_loop_networks_lds_bytes", &icnt_closed_loop_networks_lds_bytes, py::arg("icnt_texts"),
+        "dynamic LDS (bytes) of one gpu launch over these networks: the largest 5 * U * V words among their doubled "
+        "networks");
+  m.def("icnt_cln_kernel_info", &icnt_cln_kernel_info,
+        "registers, LDS and scratch of the closed-loop many-networks kernel");
+  m.def(
       "arch_energy",
       [](const std::vector<std::string>& args, double node_nm, double vdd, double dram_pj_per_bit,
          double tensor_macs_per_lane) {

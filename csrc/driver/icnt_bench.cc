@@ -16,7 +16,9 @@
 // model/icnt_reqreply.h).  The last part is the closed loop: request-reply
 // points whose nodes keep a bounded number of requests in flight, both subnets
 // on one clock in one pass over the doubled network (reference
-// batchtrafficmanager.cpp; icnt_closed_loop_batch, model/icnt_closed.h).
+// batchtrafficmanager.cpp; icnt_closed_loop_batch, model/icnt_closed.h), for
+// synthetic points on one network and for a request list the caller brings on
+// many networks and windows (icnt_closed_loop_networks).
 #include "icnt_bench.h"
 
 #include <algorithm>
@@ -24,6 +26,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <stdexcept>
 #include <vector>
@@ -1083,8 +1086,9 @@ ClRaw cl_host(const OpenLoopNet& dbl, const ClPoint& pt, bool par, uint64_t step
   return raw;
 }
 
-ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool arrivals, size_t index) {
-  check_status(raw.pass, index, "icnt_closed_loop_batch: point ");
+ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool arrivals, size_t index,
+                           const char* who = "icnt_closed_loop_batch: point ") {
+  check_status(raw.pass, index, who);
   const ClosedLoopParams& prm = pt.prm;
   const uint32_t N = net.N, nq = pt.req.np;
   const bool batch = prm.batch_size != 0;
@@ -1191,6 +1195,203 @@ std::vector<ClosedLoopResult> icnt_closed_loop_batch(const std::string& icnt_tex
       },
       [&](ClPoint& pt, ClRaw& raw) { out.push_back(cl_finish(net, pt, raw, opts.arrivals, out.size())); });
   return out;
+}
+
+// ---- one request list, closed loop, over many networks and windows ----
+
+namespace {
+
+const char* const kClnWho = "icnt_closed_loop_networks: network ";
+
+// a network of the call: the .icnt file's, its doubled network, and the list
+// as a batch point of it (window and delay are set per unit)
+struct ClnNet {
+  size_t index = 0;
+  OpenLoopNet net, dbl;
+  ClPoint pt;
+  uint64_t fl_req = 0, fl_rep = 0;
+};
+
+ClnNet cln_prepare(const ClosedLoopList& list, const std::string& icnt_text, size_t index, uint64_t delay) {
+  const std::string who = kClnWho + std::to_string(index);
+  auto bad = [&](const std::string& what) { throw std::invalid_argument(who + ": " + what); };
+  const size_t nq = list.src.size();
+  if (list.dst.size() != nq || list.req_bytes.size() != nq || list.reply_bytes.size() != nq ||
+      list.tcreate.size() != nq)
+    bad("src, dst, req_bytes, reply_bytes and tcreate differ in length");
+  if (nq > kReplayMaxPackets / 2)
+    bad("too many requests for one pass (" + std::to_string(nq) + ", at most " + std::to_string(kReplayMaxPackets / 2) + ")");
+  ClnNet cn;
+  cn.index = index;
+  try {
+    cn.net = icnt_open_loop_net(icnt_text);
+    cn.dbl = doubled_net(cn.net);
+  } catch (const std::invalid_argument& e) {
+    bad(e.what());
+  }
+  const uint32_t N = cn.net.N;
+  if (list.nodes && N != list.nodes)
+    bad("the network has " + std::to_string(N) + " nodes, the request list is for " + std::to_string(list.nodes));
+  if (!cn.net.c.flit_size) bad("flit_size is zero");
+  std::vector<char> has(N, 0);
+  for (size_t i = 0; i < nq; ++i) {
+    const uint32_t s = list.src[i], t = list.dst[i];
+    if (s >= N || t >= N)
+      bad("request " + std::to_string(i) + " has a node out of range (" + std::to_string(s) + " -> " + std::to_string(t) +
+          ", the network has " + std::to_string(N) + " nodes)");
+    if (s == t) bad("request " + std::to_string(i) + " has src == dst (" + std::to_string(s) + ")");
+    if (i && list.tcreate[i] < list.tcreate[i - 1])
+      bad("request " + std::to_string(i) + " has a decreasing tcreate (the list must be in creation order)");
+    has[s] = 1;
+  }
+  ClPoint& pt = cn.pt;
+  pt.prm.batch_size = 1;  // a batch point: every request measured, batch_time the last reply's arrival
+  pt.prm.reply_delay = delay;
+  for (char h : has) pt.issuers += h ? 1 : 0;
+  pt.src.assign(2 * nq, 0);
+  pt.dst.assign(2 * nq, 0);
+  pt.nfl.assign(2 * nq, 0);
+  pt.req.tinj.assign(nq, 0);
+  // the pass's packets as every engine derives them from the list
+  RtWork fw{};
+  fw.src = pt.src.data();
+  fw.dst = pt.dst.data();
+  fw.nfl = pt.nfl.data();
+  fw.tinj = pt.req.tinj.data();
+  RtClList l;
+  l.src = list.src.data();
+  l.dst = list.dst.data();
+  l.req_bytes = list.req_bytes.data();
+  l.reply_bytes = list.reply_bytes.data();
+  l.tcreate = list.tcreate.data();
+  l.nq = (uint32_t)nq;
+  rt_cl_fill_list<SeqPar>(cn.net.c, l, N, fw);
+  pt.req.np = (uint32_t)nq;
+  pt.req.src.assign(pt.src.begin(), pt.src.begin() + nq);
+  pt.req.dst.assign(pt.dst.begin(), pt.dst.begin() + nq);
+  pt.req.nfl.assign(pt.nfl.begin(), pt.nfl.begin() + nq);
+  for (size_t i = 0; i < nq; ++i) {
+    cn.fl_req += pt.nfl[i];
+    cn.fl_rep += pt.nfl[nq + i];
+  }
+  if (cn.fl_req + cn.fl_rep > 0xffffffffull) bad("too many flits for one pass");
+  pt.d = list_dims(cn.dbl, 2 * (uint32_t)nq, 1);
+  pt.d.nf = std::max<uint32_t>(1, (uint32_t)(cn.fl_req + cn.fl_rep));  // exactly the packets' flits
+  return cn;
+}
+
+ClnUnit cln_unit(const ClnNet& cn, const ClPoint& pt) {
+  ClnUnit u;
+  u.dbl = &cn.dbl;
+  u.d = pt.d;
+  u.nq = pt.req.np;
+  u.window = pt.prm.max_outstanding;
+  u.delay = pt.prm.reply_delay;
+  u.nfl = &pt.nfl;
+  return u;
+}
+
+ClosedLoopNetResult cln_finish(const ClnNet& cn, ClPoint& pt, ClRaw& raw, bool arrivals) {
+  const size_t nq = pt.req.np;
+  std::vector<uint32_t> nfl;
+  if (arrivals) nfl = pt.nfl;
+  ClosedLoopResult c = cl_finish(cn.net, pt, raw, arrivals, cn.index, kClnWho);
+  ClosedLoopNetResult r;
+  r.network = (uint32_t)cn.index;
+  r.window = pt.prm.max_outstanding;
+  r.nodes = c.nodes;
+  r.issuers = c.issuers;
+  r.requests = c.requests;
+  r.measured = c.measured;
+  r.request_flits = cn.fl_req;
+  r.reply_flits = cn.fl_rep;
+  r.batch_time = c.batch_time;
+  r.request_latency = c.request_latency;
+  r.reply_latency = c.reply_latency;
+  r.round_trip_latency = c.round_trip_latency;
+  r.max_round_trip_latency = c.max_round_trip_latency;
+  r.issue_stall = c.issue_stall;
+  r.max_issue_stall = c.max_issue_stall;
+  r.accepted_request = c.accepted_request;
+  r.accepted_reply = c.accepted_reply;
+  r.avg_outstanding = c.avg_outstanding;
+  r.first_finish = c.first_finish;
+  r.last_finish = c.last_finish;
+  r.deadlocked = c.deadlocked;
+  for (int i = 0; i < 8; ++i) r.activity[i] = c.activity[i];
+  r.e_buffer = c.e_buffer;
+  r.e_xbar = c.e_xbar;
+  r.e_link = c.e_link;
+  r.e_alloc = c.e_alloc;
+  r.e_leak = c.e_leak;
+  r.power_w = c.power_w;
+  if (arrivals) {
+    r.request_flit_counts.assign(nfl.begin(), nfl.begin() + nq);
+    r.reply_flit_counts.assign(nfl.begin() + nq, nfl.end());
+    r.tiss = std::move(c.tiss);
+    r.request_arrivals = std::move(c.request_arrivals);
+    r.reply_arrivals = std::move(c.reply_arrivals);
+    r.state = std::move(c.state);
+  }
+  return r;
+}
+
+}  // namespace
+
+std::vector<ClosedLoopNetResult> icnt_closed_loop_networks(const ClosedLoopList& list,
+                                                           const std::vector<std::string>& icnt_texts,
+                                                           const std::vector<uint32_t>& windows, uint64_t reply_delay,
+                                                           const std::string& engine, const OpenLoopBatchOpts& opts) {
+  check_engine("icnt_closed_loop_networks", engine);
+  const size_t nw = windows.size();
+  std::vector<ClosedLoopNetResult> out;
+  out.reserve(icnt_texts.size() * nw);
+  g_last = OpenLoopBatchStats();
+  if (engine != "gpu") {
+    for (size_t i = 0; i < icnt_texts.size(); ++i) {
+      const ClnNet cn = cln_prepare(list, icnt_texts[i], i, reply_delay);
+      for (uint32_t window : windows) {
+        ClPoint pt = cn.pt;
+        pt.prm.max_outstanding = window;
+        ClRaw raw = cl_host(cn.dbl, pt, engine == "cpu-par", opts.step_cap);
+        out.push_back(cln_finish(cn, pt, raw, opts.arrivals));
+      }
+    }
+    return out;
+  }
+  // gpu: the (network, window) units are prepared one after the other,
+  // network-major, and packed into chunks under the memory budget (the list's
+  // device copy counts once per chunk, a network's tables once per unit); a
+  // full chunk is one launch
+  struct Item {
+    std::shared_ptr<const ClnNet> cn;
+    ClPoint pt;
+  };
+  const ClList cl{&list.src, &list.dst, &list.req_bytes, &list.reply_bytes, &list.tcreate};
+  std::shared_ptr<const ClnNet> cur;
+  pack_chunks<Item, ClRaw>(
+      "icnt_closed_loop_networks: unit", opts, icnt_cln_list_bytes(cl), icnt_texts.size() * nw,
+      [&](size_t i) {
+        const size_t ni = i / nw;
+        if (!cur || cur->index != ni) cur = std::make_shared<const ClnNet>(cln_prepare(list, icnt_texts[ni], ni, reply_delay));
+        Item it{cur, cur->pt};
+        it.pt.prm.max_outstanding = windows[i % nw];
+        return it;
+      },
+      [](const Item& it) { return icnt_cln_unit_bytes(cln_unit(*it.cn, it.pt)); },
+      [&](const std::vector<Item>& chunk, std::vector<ClRaw>& raws) {
+        std::vector<ClnUnit> units;
+        for (const Item& it : chunk) units.push_back(cln_unit(*it.cn, it.pt));
+        return icnt_cln_run_chunk(cl, units, opts.step_cap, opts.lds, raws);
+      },
+      [&](Item& it, ClRaw& raw) { out.push_back(cln_finish(*it.cn, it.pt, raw, opts.arrivals)); });
+  return out;
+}
+
+uint64_t icnt_closed_loop_networks_lds_bytes(const std::vector<std::string>& icnt_texts) {
+  uint64_t b = 0;
+  for (const std::string& t : icnt_texts) b = std::max(b, icnt_hot_bytes(list_dims(doubled_net(icnt_open_loop_net(t)), 1, 1)));
+  return b;
 }
 
 }  // namespace asim

@@ -259,4 +259,67 @@ std::vector<ClosedLoopResult> icnt_closed_loop_batch(const std::string& icnt_tex
                                                      const std::string& engine = "cpu",
                                                      const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
 
+// ---- one request list, closed loop, over many networks and windows ----
+
+// a request list in bytes (for example the requests of an -icnt_capture file
+// with their replies' sizes, icnt/capture.py request_list): request i goes
+// from src[i] to dst[i] with req_bytes[i] bytes, is created at tcreate[i]
+// (non-decreasing, so a node's requests are in issue order) and is answered
+// by a reply of reply_bytes[i] bytes.  nodes: the node count the list was made
+// for (0: unknown)
+struct ClosedLoopList {
+  uint32_t nodes = 0;
+  std::vector<uint32_t> src, dst, req_bytes, reply_bytes;
+  std::vector<uint64_t> tcreate;
+};
+
+// a (network, window) point: every request is measured (as for a batch point
+// of icnt_closed_loop_batch) and batch_time is the last reply's arrival, the
+// time the list's requests take on that network when a node may keep `window`
+// of them in flight
+struct ClosedLoopNetResult {
+  uint32_t network = 0, window = 0;  // index into icnt_texts; 0: unlimited
+  uint32_t nodes = 0, issuers = 0;
+  uint64_t requests = 0, measured = 0;
+  uint64_t request_flits = 0, reply_flits = 0;  // the list's totals on this network
+  uint64_t batch_time = 0;
+  double request_latency = 0, reply_latency = 0, round_trip_latency = 0, max_round_trip_latency = 0;
+  double issue_stall = 0, max_issue_stall = 0;
+  double accepted_request = 0, accepted_reply = 0;
+  double avg_outstanding = 0;
+  uint64_t first_finish = 0, last_finish = 0;
+  uint32_t deadlocked = 0;
+  uint64_t activity[8] = {};
+  double e_buffer = 0, e_xbar = 0, e_link = 0, e_alloc = 0, e_leak = 0, power_w = 0;
+  // on request (opts.arrivals): every request's issue time, both arrival
+  // arrays by request, this network's flit counts, the doubled network's state words
+  std::vector<uint32_t> request_flit_counts, reply_flit_counts;
+  std::vector<uint64_t> tiss, request_arrivals, reply_arrivals, state;
+};
+
+// the list through every network of icnt_texts under every window of
+// `windows`, one closed-loop pass each (model/icnt_closed.h) on the network's
+// doubled network; one result per (network, window), network-major.  Network i
+// carries both packets of a request with
+//   flits = min(rt_flits(c_i, bytes), rt_flits(c_i, kRtMaxPktBytes))
+// (model/icnt_closed.h rt_cl_fill_list).  "cpu" is the defining form, a loop
+// of single passes (rt_simulate_closed); "cpu-par" the lane-parallel pass on
+// the host; "gpu" one wavefront per (network, window), as many per launch as
+// the memory budget takes (engine/icnt_cln_sweep.hip).  std::invalid_argument,
+// naming the network: a node count other than list.nodes (when it states one),
+// src == dst or a node out of range, a decreasing tcreate, arrays of unequal
+// length, more than kReplayMaxPackets / 2 requests, and what
+// icnt_closed_loop_batch refuses of a network; std::runtime_error: a pass cut
+// off by its loop guard (opts.step_cap applies to every engine).
+std::vector<ClosedLoopNetResult> icnt_closed_loop_networks(const ClosedLoopList& list,
+                                                           const std::vector<std::string>& icnt_texts,
+                                                           const std::vector<uint32_t>& windows,
+                                                           uint64_t reply_delay = 0, const std::string& engine = "cpu",
+                                                           const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
+
+// the dynamic LDS (bytes) one gpu launch over these networks takes for the
+// per-(unit, VC) words: the largest 5 * U * V words among their doubled
+// networks; in LDS when this fits kIcntSweepLdsBytes.  Host work only.
+uint64_t icnt_closed_loop_networks_lds_bytes(const std::vector<std::string>& icnt_texts);
+
 }  // namespace asim

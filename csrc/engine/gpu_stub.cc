@@ -60,4 +60,8 @@ bool icnt_cl_run_chunk(const OpenLoopNet&, const std::vector<ClUnit>&, uint64_t,
   throw std::runtime_error("no GPU engine in this build");
 }
 std::map<std::string, uint64_t> icnt_cl_kernel_info() { return {}; }
+bool icnt_cln_run_chunk(const ClList&, const std::vector<ClnUnit>&, uint64_t, bool, std::vector<ClRaw>&) {
+  throw std::runtime_error("no GPU engine in this build");
+}
+std::map<std::string, uint64_t> icnt_cln_kernel_info() { return {}; }
 }  // namespace asim

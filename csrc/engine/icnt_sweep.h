@@ -6,8 +6,9 @@
 // (icnt_rr_sweep.hip) takes packet lists with per-packet sizes and
 // request-reply points, both subnets of a point in one wavefront; a third
 // (icnt_net_sweep.hip) one packet list over many networks; a fourth
-// (icnt_cl_sweep.hip) closed-loop points on the doubled network.  What the
-// launch paths share lives in two headers: icnt_sweep_layout.h (plain C++,
+// (icnt_cl_sweep.hip) closed-loop points on the doubled network; a fifth
+// (icnt_cln_sweep.hip) one request list, closed loop, over many networks and
+// windows.  What the launch paths share lives in two headers: icnt_sweep_layout.h (plain C++,
 // every build) has a chunk's layout, the descriptors and the `*_bytes` the
 // caller budgets with; icnt_sweep_dev.h (the .hip files only) has the
 // pass with its LDS placement, the chunk's device block and the resource
@@ -134,5 +135,44 @@ bool icnt_cl_run_chunk(const OpenLoopNet& net, const std::vector<ClUnit>& units,
                        std::vector<ClRaw>& raws);
 
 std::map<std::string, uint64_t> icnt_cl_kernel_info();
+
+// ---- one request list, closed loop, over many networks and windows (icnt_cln_kernel, icnt_cln_sweep.hip) ----
+
+// the request list every unit of a chunk runs: uploaded once per chunk; a
+// unit's flit counts come from the bytes and its own network's flit size, on
+// the device (model/icnt_closed.h rt_cl_fill_list)
+struct ClList {
+  const std::vector<uint32_t>*src = nullptr, *dst = nullptr, *req_bytes = nullptr, *reply_bytes = nullptr;
+  const std::vector<uint64_t>* tcreate = nullptr;
+};
+
+// one unit of a launch: a (network, window) point.  dbl: the network's doubled
+// network (tables; `lat` / `inj_lat` empty for the uniform channel latency),
+// which the unit places for itself; nfl: the 2 * nq flit counts the host
+// derived, which the device must reproduce
+struct ClnUnit {
+  const OpenLoopNet* dbl = nullptr;
+  RtDims d{};  // the doubled network's pass
+  uint32_t nq = 0, window = 0;
+  uint64_t delay = 0;
+  const std::vector<uint32_t>* nfl = nullptr;
+};
+
+// the dynamic LDS of a chunk's launch: the largest 5 * U * V words among its
+// units' doubled networks (every workgroup carves its own U * V out of it)
+inline uint64_t icnt_cln_hot_bytes(const std::vector<ClnUnit>& units) {
+  uint64_t b = 0;
+  for (const ClnUnit& u : units) b = std::max(b, icnt_hot_bytes(u.d));
+  return b;
+}
+
+// one launch: grid = the chunk's (network, window) units, 64 lanes each; every
+// workgroup reads its own configuration, dimensions and tables from its
+// descriptor and fills its packets from the shared list.  Same LDS rule and
+// return value as icnt_net_run_chunk.
+bool icnt_cln_run_chunk(const ClList& list, const std::vector<ClnUnit>& units, uint64_t step_cap, bool allow_lds,
+                        std::vector<ClRaw>& raws);
+
+std::map<std::string, uint64_t> icnt_cln_kernel_info();
 
 }  // namespace asim

@@ -1,6 +1,6 @@
-// What the four network sweep kernels and their launch paths share
-// (icnt_sweep.hip, icnt_rr_sweep.hip, icnt_net_sweep.hip, icnt_cl_sweep.hip;
-// included by those four only): on the device the router pass of one unit with the placement
+// What the five network sweep kernels and their launch paths share
+// (icnt_sweep.hip, icnt_rr_sweep.hip, icnt_net_sweep.hip, icnt_cl_sweep.hip,
+// icnt_cln_sweep.hip; included by those five only): on the device the router pass of one unit with the placement
 // of its per-(unit, VC) words, on the host the chunk's device block with its
 // copies, and the kernels' resource query.  The chunk's layout is
 // icnt_sweep_layout.h.

@@ -1,14 +1,15 @@
 // The layout of one chunk of a network sweep launch (icnt_sweep.h), plain C++
 // for the HIP build and the CPU-only build alike: what the host fills and the
-// kernels read (the descriptors SweepPt / RrPt / NetPt and the output record
-// SweepOut), and the ONE routine per kind that places a unit into a chunk.
+// kernels read (the descriptors SweepPt / RrPt / NetPt / ClPt / ClNetPt and the
+// output record SweepOut), and the ONE routine per kind that places a unit
+// into a chunk.
 // The driver budgets with `*_bytes`, which places a unit into an empty layout
 // and reads the total; `*_run_chunk` places the same units with the same
 // routine and allocates the total, so what is accounted is what is allocated
 // (SweepChunk, icnt_sweep_dev.h, refuses a block of any other size).
 //
 // A chunk is: the descriptors, the output records, the fixed part (the
-// network for the first two kinds, the shared packet list for the third),
+// network of a one-network kind, the shared list of a many-networks kind),
 // then what each unit placed.  Every piece starts on 16 bytes, and the records
 // are multiples of 16 bytes, so n units cost n times one unit.
 #pragma once
@@ -72,11 +73,26 @@ struct alignas(16) ClPt {  // a closed-loop point on the doubled network
   uint64_t delay;
   uint64_t st_off, scr_off, cl_off;  // cl: rt_cl_carve(d, nq)
 };
+// a closed-loop unit of a many-networks chunk: one (network, window) point on
+// its own doubled network.  net: the unit's SimCfg and doubled route tables;
+// net.lat / net.ilat 0 (the descriptors' offset, never a table's): the
+// uniform channel latency
+struct alignas(16) ClNetPt {
+  RtDims d;
+  uint32_t nq, window;
+  uint64_t delay;
+  NetOff net;
+  uint64_t st_off, scr_off, cl_off;  // cl: rt_cl_carve(d, nq)
+};
 struct ListOff {  // the shared list of a many-networks chunk
   uint64_t src, dst, bytes, tinj;
 };
+struct ClListOff {  // the shared request list of a closed-loop many-networks chunk
+  ListOff req;      // src, dst, request bytes, creation times
+  uint64_t reply_bytes;
+};
 static_assert(sizeof(SweepOut) % 16 == 0 && sizeof(SweepPt) % 16 == 0 && sizeof(RrPt) % 16 == 0 &&
-                  sizeof(NetPt) % 16 == 0 && sizeof(ClPt) % 16 == 0,
+                  sizeof(NetPt) % 16 == 0 && sizeof(ClPt) % 16 == 0 && sizeof(ClNetPt) % 16 == 0,
               "per-unit sums of the record arrays are exact");
 
 // ---- the fixed part of a chunk ----
@@ -97,6 +113,13 @@ inline ListOff place_list(ChunkLayout& l, uint64_t np) {
   o.dst = l.take(np * 4);
   o.bytes = l.take(np * 4);
   o.tinj = l.take(np * 8);
+  return o;
+}
+
+inline ClListOff place_cl_list(ChunkLayout& l, uint64_t nq) {
+  ClListOff o;
+  o.req = place_list(l, nq);
+  o.reply_bytes = l.take(nq * 4);
   return o;
 }
 
@@ -151,6 +174,19 @@ inline ClPt place_cl_unit(ChunkLayout& l, const ClUnit& u) {
   return h;
 }
 
+inline ClNetPt place_cln_unit(ChunkLayout& l, const ClnUnit& u) {
+  ClNetPt h{};
+  h.d = u.d;
+  h.nq = u.nq;
+  h.window = u.window;
+  h.delay = u.delay;
+  h.net = place_net(l, *u.dbl);
+  if (u.dbl->lat.empty()) h.net.lat = h.net.ilat = 0;
+  place_pass(l, h.d, h.st_off, h.scr_off);
+  h.cl_off = l.take(rt_cl_carve(h.d, h.nq, nullptr, nullptr) * 4);
+  return h;
+}
+
 // ---- what the driver budgets with ----
 
 // device bytes of a chunk besides its units: the network of an open-loop or
@@ -165,9 +201,14 @@ inline uint64_t icnt_net_list_bytes(const NetList& list) {
   place_list(l, list.src ? list.src->size() : 0);
   return l.bytes;
 }
+inline uint64_t icnt_cln_list_bytes(const ClList& list) {
+  ChunkLayout l;
+  place_cl_list(l, list.src ? list.src->size() : 0);
+  return l.bytes;
+}
 
 // device bytes a unit adds to a chunk (records, state, scratch; a network
-// unit's configuration and tables)
+// unit's configuration and tables, a closed-loop network unit's doubled ones)
 inline uint64_t icnt_sweep_point_bytes(const OpenLoopPoint& pt) {
   ChunkLayout l;
   l.records<SweepPt>(1);
@@ -190,6 +231,13 @@ inline uint64_t icnt_net_unit_bytes(const NetUnit& u) {
   ChunkLayout l;
   l.records<NetPt>(1);
   place_net_unit(l, u);
+  return l.bytes;
+}
+
+inline uint64_t icnt_cln_unit_bytes(const ClnUnit& u) {
+  ChunkLayout l;
+  l.records<ClNetPt>(1);
+  place_cln_unit(l, u);
   return l.bytes;
 }
 

@@ -10,8 +10,8 @@
 // holds 2 * nq packets:
 //   request i       src[i] -> dst[i]          i in [0, nq), time-ordered
 //   reply  nq + i   N + dst[i] -> N + src[i]  flits by the request's kind
-// A reply's source, destination and flits are known up front (rt_cl_fill_reply);
-// its injection time is not.
+// A reply's source, destination and flits are known up front (rt_cl_fill_reply;
+// rt_cl_fill_list for a request list in bytes); its injection time is not.
 //
 // Rules (one element each, like RtCtx's members; the drivers decide the order
 // and the parallelism):
@@ -104,6 +104,39 @@ SIM_HDI void rt_cl_fill_reply(uint32_t* src, uint32_t* dst, uint32_t* nfl, uint3
   src[nq + i] = n + dst[i];
   dst[nq + i] = n + src[i];
   nfl[nq + i] = write ? fl_write : fl_read;
+}
+
+// A request list in bytes (for example the requests of an -icnt_capture file,
+// icnt/capture.py request_list): request i goes from src[i] to dst[i] with
+// req_bytes[i] bytes, is created at tcreate[i] (non-decreasing) and is
+// answered by reply_bytes[i] bytes.  What a packet weighs in flits depends on
+// the network that carries it.
+struct RtClList {
+  const uint32_t *src = nullptr, *dst = nullptr, *req_bytes = nullptr, *reply_bytes = nullptr;
+  const uint64_t* tcreate = nullptr;
+  uint32_t nq = 0;
+};
+
+// the pass's 2 * nq packets from the list, for the network of c (n nodes per
+// subnet), a lane per request: w.src / w.dst / w.nfl of both packets and the
+// request's w.tinj (its creation time until its issue).  Flits as a
+// many-networks replay derives them (engine/icnt_net_sweep.hip):
+//   nfl = min(rt_flits(c, bytes), rt_flits(c, kRtMaxPktBytes))
+// The caller syncs before the pass.
+template <class P>
+SIM_HDI void rt_cl_fill_list(const SimCfg& c, const RtClList& l, uint32_t n, const RtWork& w) {
+  const uint32_t nq = l.nq, nfl_max = rt_flits(c, kRtMaxPktBytes);
+  P::each((int)nq, [&](int i) {
+    const uint32_t s = l.src[i], t = l.dst[i];
+    const uint32_t fq = rt_flits(c, l.req_bytes[i]), fp = rt_flits(c, l.reply_bytes[i]);
+    w.src[i] = s;
+    w.dst[i] = t;
+    w.tinj[i] = l.tcreate[i];
+    w.nfl[i] = fq < nfl_max ? fq : nfl_max;
+    w.src[nq + i] = n + t;
+    w.dst[nq + i] = n + s;
+    w.nfl[nq + i] = fp < nfl_max ? fp : nfl_max;
+  });
 }
 
 // packet p to the tail of node s's source queue
