@@ -219,7 +219,9 @@ def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = Non
                       write_fraction: Optional[float] = None, reply_delay: int = 0, mem_nodes: int = 0,
                       read_request_size: Optional[int] = None, read_reply_size: Optional[int] = None,
                       write_request_size: Optional[int] = None, write_reply_size: Optional[int] = None,
-                      mem_budget_mb: int = 0, arrivals: bool = False, lds: bool = True) -> List[Dict]:
+                      mem_budget_mb: int = 0, arrivals: bool = False, lds: bool = True,
+                      read_occupancy: Optional[int] = None, write_occupancy: Optional[int] = None,
+                      write_reply_delay: Optional[int] = None) -> List[Dict]:
     """Closed-loop request-reply points with bounded windows as ONE batch
     through `engine` (``gpu``: one wavefront per point,
     csrc/engine/icnt_cl_sweep.hip).  A node keeps at most M requests in flight
@@ -230,6 +232,13 @@ def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = Non
     every issuing node creating `batch_size` requests at cycle 0.  Defaults
     from the ``.icnt`` keys: ``max_outstanding_requests`` for M, ``batch_size``
     when ``sim_type = batch``, the four packet sizes and ``write_fraction``.
+
+    `read_occupancy`, `write_occupancy` and `write_reply_delay` turn the
+    memory endpoint on: a memory node is one server that a request holds for
+    its kind's occupancy (cycles), first come first served, with `reply_delay`
+    (a write: `write_reply_delay`) cycles of pipelined latency behind it, and
+    replies leave a node in the order their requests arrived.  The results
+    carry ``mem_time``, ``mem_wait``, ``mem_hold`` and ``mem_utilisation``.
 
     Without `arrivals` the result is the curve: one dict per (traffic, rate,
     M) with the figures averaged over the seeds (``batch_time``,
@@ -243,6 +252,10 @@ def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = Non
     common = {k: int(v if v is not None else float(kv.get(k, 1))) for k, v in given.items()}
     common["write_fraction"] = float(write_fraction if write_fraction is not None else kv.get("write_fraction", 0.5))
     common.update(reply_delay=int(reply_delay), mem_nodes=int(mem_nodes))
+    for k, v in (("read_occupancy", read_occupancy), ("write_occupancy", write_occupancy),
+                 ("write_reply_delay", write_reply_delay)):
+        if v is not None:
+            common[k] = int(v)
     if "batch_count" in kv:
         common["batch_count"] = int(float(kv["batch_count"]))
     if max_outstanding is None:
@@ -273,9 +286,10 @@ def closed_loop_sweep(icnt_text: str, max_outstanding: Optional[List[int]] = Non
         m = {k: group[0][k] for k in ("traffic", "rate", "max_outstanding", "nodes", "issuers")}
         m["seeds"] = per
         for k in ("batch_time", "request_latency", "reply_latency", "round_trip_latency", "issue_stall",
-                  "accepted_request", "accepted_reply", "avg_outstanding", "first_finish", "last_finish", "power_w"):
+                  "accepted_request", "accepted_reply", "avg_outstanding", "first_finish", "last_finish", "power_w",
+                  "mem_time", "mem_wait", "mem_hold", "mem_utilisation"):
             m[k] = sum(p[k] for p in group) / per
-        for k in ("max_round_trip_latency", "max_issue_stall"):
+        for k in ("max_round_trip_latency", "max_issue_stall", "max_mem_time", "max_mem_utilisation", "mem_nodes_used"):
             m[k] = max(p[k] for p in group)
         for k in ("requests", "reads", "writes", "deadlocked"):
             m[k] = sum(p[k] for p in group)
@@ -294,12 +308,15 @@ def _print_closed_loop(c: Dict, batch: bool) -> None:
     print(f"Issue stall = {c['issue_stall']:.2f} cycles (max {c['max_issue_stall']:.0f}); "
           f"outstanding requests per node = {c['avg_outstanding']:.2f}")
     print(f"Accepted rate: request {c['accepted_request']:.4f}, reply {c['accepted_reply']:.4f}")
+    print(f"Memory time = {c['mem_time']:.2f} (max {c['max_mem_time']:.0f}): wait {c['mem_wait']:.2f}, "
+          f"in-order hold {c['mem_hold']:.2f}; utilisation {c['mem_utilisation']:.3f} "
+          f"(max {c['max_mem_utilisation']:.3f}) over {c['mem_nodes_used']} memory nodes")
 
 
 def closed_loop_replay(src, dst, req_bytes, reply_bytes, tcreate, icnt_texts: List[str],
                        max_outstanding: Optional[List[int]] = None, reply_delay: int = 0, engine: str = "cpu",
                        arrivals: bool = False, mem_budget_mb: int = 0, lds: bool = True,
-                       nodes: int = 0) -> List[Dict]:
+                       nodes: int = 0, occupancy=None, latency=None, mem_points=None) -> List[Dict]:
     """One request list, closed loop, through many networks under many windows:
     one dict per (``.icnt`` text, window of `max_outstanding`), network-major,
     with its ``network`` index and ``max_outstanding``.  Request i goes from
@@ -312,12 +329,26 @@ def closed_loop_replay(src, dst, req_bytes, reply_bytes, tcreate, icnt_texts: Li
     ``engine="gpu"`` runs one wavefront per (network, window), as many per
     launch as the memory budget takes (csrc/engine/icnt_cln_sweep.hip).
     `nodes`: the list's node count; a network with another one is refused (0:
-    not checked)."""
+    not checked).
+
+    `mem_points` adds a third axis, the memory endpoint: each point is
+    ``(occupancy, latency)``, applied to every request, or the word ``"list"``
+    for the per-request arrays `occupancy` and `latency`.  A memory node is
+    one server that a request holds for its occupancy, first come first
+    served, with its latency behind it, and replies leave a node in the order
+    their requests arrived.  The results are then network-major, then window,
+    then memory point, each with its ``mem_point`` index and ``mem`` (the
+    point), and ``mem_time``, ``mem_wait``, ``mem_hold`` and
+    ``mem_utilisation`` say what the memory nodes did.  Without `mem_points`
+    every reply is created `reply_delay` after its request's delivery."""
     mod = _native.load(prefer_torch_runtime=engine == "gpu")
     windows = [0] if max_outstanding is None else [int(m) for m in max_outstanding]
+    if mem_points is not None:
+        mem_points = [m if isinstance(m, str) else tuple(m) for m in mem_points]
     return [dict(d) for d in mod.icnt_closed_loop_networks(
         (src, dst, req_bytes, reply_bytes, tcreate), list(icnt_texts), windows, reply_delay=int(reply_delay),
-        engine=engine, arrivals=arrivals, mem_budget_mb=mem_budget_mb, lds=lds, nodes=nodes)]
+        engine=engine, arrivals=arrivals, mem_budget_mb=mem_budget_mb, lds=lds, nodes=nodes, occupancy=occupancy,
+        latency=latency, mem_points=mem_points)]
 
 
 def _main_closed_replay(a) -> int:
@@ -326,6 +357,7 @@ def _main_closed_replay(a) -> int:
     if capture.is_capture(a.replay):
         rl = capture.request_list(capture.load(a.replay), timing=a.timing)
         lst, nodes = (rl.src, rl.dst, rl.req_bytes, rl.reply_bytes, rl.tcreate), rl.nodes
+        occ = lat = None  # (a capture file has no service times)
     else:
         with np.load(a.replay) as z:
             missing = [k for k in ("src", "dst", "bytes", "reply_bytes", "tinj") if k not in z]
@@ -339,22 +371,36 @@ def _main_closed_replay(a) -> int:
             lst = (z["src"][order], z["dst"][order], z["bytes"][order], z["reply_bytes"][order],
                    tinj if a.timing == "captured" else np.zeros_like(tinj))
             nodes = int(z["nodes"]) if "nodes" in z else 0
+            occ = z["occupancy"][order] if "occupancy" in z else None
+            lat = z["latency"][order] if "latency" in z else None
+    mem_points = None
+    if a.mem_occupancy:
+        words = [x for x in a.mem_occupancy.split(",") if x]
+        if "list" in words and (occ is None or lat is None):
+            print(f"--mem-occupancy list needs the request list's occupancy and latency arrays: {a.replay} has none "
+                  f"(an .npz with occupancy and latency: capture.save_request_npz)", file=sys.stderr)
+            return 2
+        mem_points = ["list" if x == "list" else (int(x), a.reply_delay) for x in words]
     files = [n for n in (a.networks or "").split(",") if n] or [a.config]
     windows = [int(x) for x in a.max_outstanding.split(",") if x] if a.max_outstanding else [0]
     res = closed_loop_replay(*lst, [open(f).read() for f in files], windows, reply_delay=a.reply_delay,
-                             engine=a.engine, mem_budget_mb=a.mem_budget_mb, nodes=nodes)
+                             engine=a.engine, mem_budget_mb=a.mem_budget_mb, nodes=nodes, occupancy=occ, latency=lat,
+                             mem_points=mem_points)
     for c in res:
         m = c["max_outstanding"]
         c["config"] = files[c["network"]]
+        mem = "" if "mem" not in c else (", memory occupancy from the list" if c["mem"] == "list"
+                                         else f", memory occupancy {c['mem'][0]}")
         print(f"====== Closed-loop replay of {a.replay} on {c['config']}, {a.timing} timing, "
-              f"max outstanding {m if m else 'unlimited'} ======")
+              f"max outstanding {m if m else 'unlimited'}{mem} ======")
         _print_closed_loop(c, True)
         print(f"Packets = {c['requests']} requests ({c['request_flits']} flits), {c['reply_flits']} reply flits"
               + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
     if a.json:
         with open(a.json, "w") as f:
             json.dump({"replay": a.replay, "closed_loop": True, "timing": a.timing, "reply_delay": a.reply_delay,
-                       "networks": files, "max_outstanding": windows, "grid": res}, f, indent=1)
+                       "networks": files, "max_outstanding": windows,
+                       **({} if mem_points is None else {"mem_points": mem_points}), "grid": res}, f, indent=1)
     return 0
 
 
@@ -371,14 +417,25 @@ def _main_closed_loop(a, text: str) -> int:
             print("--closed-loop needs --batch-size, --rates, or sim_type = batch in the .icnt file", file=sys.stderr)
             return 2
         batch = int(float(kv.get("batch_size", 1)))
-    curve = closed_loop_sweep(text, windows, batch_size=batch, rates=None if batch is not None else rates,
-                              engine=a.engine, traffic=traffics if len(traffics) > 1 else a.traffic, cycles=a.cycles,
-                              warmup=a.warmup, seed=a.seed, seeds=seeds, write_fraction=a.write_fraction,
-                              reply_delay=a.reply_delay, mem_nodes=a.mem_nodes, mem_budget_mb=a.mem_budget_mb, **sizes)
+    occs = [None]
+    if a.mem_occupancy:
+        if "list" in a.mem_occupancy.split(","):
+            print("--mem-occupancy list needs --replay (a request list with occupancy and latency arrays)", file=sys.stderr)
+            return 2
+        occs = [int(x) for x in a.mem_occupancy.split(",") if x]
+    curve = []
+    for occ in occs:  # the memory axis: one batch per occupancy, reads and writes alike
+        part = closed_loop_sweep(text, windows, batch_size=batch, rates=None if batch is not None else rates,
+                                 engine=a.engine, traffic=traffics if len(traffics) > 1 else a.traffic, cycles=a.cycles,
+                                 warmup=a.warmup, seed=a.seed, seeds=seeds, write_fraction=a.write_fraction,
+                                 reply_delay=a.reply_delay, mem_nodes=a.mem_nodes, mem_budget_mb=a.mem_budget_mb,
+                                 read_occupancy=occ, write_occupancy=occ, write_reply_delay=a.write_reply_delay, **sizes)
+        curve += part if occ is None else [dict(c, mem_occupancy=occ) for c in part]
     for c in curve:
         m = c["max_outstanding"]
         what = f"batch size {batch}" if batch is not None else f"injection rate {c['rate']:.3f}"
-        print(f"====== Traffic {c['traffic']}, closed loop, {what}, max outstanding {m if m else 'unlimited'} ======")
+        mem = f", memory occupancy {c['mem_occupancy']}" if "mem_occupancy" in c else ""
+        print(f"====== Traffic {c['traffic']}, closed loop, {what}, max outstanding {m if m else 'unlimited'}{mem} ======")
         _print_closed_loop(c, batch is not None)
         print(f"Packets = {c['reads']} reads, {c['writes']} writes"
               + (f", {c['deadlocked']} deadlocked" if c["deadlocked"] else ""))
@@ -527,6 +584,12 @@ def main(argv=None) -> int:
     ap.add_argument("--timing", choices=("captured", "batch"), default="captured",
                     help="--closed-loop --replay: the requests' creation times as captured, or all at cycle 0 in "
                          "captured order")
+    ap.add_argument("--mem-occupancy", metavar="O,O,...", default=None,
+                    help="closed loop: a memory node is one server that a request holds for O cycles, with "
+                         "--reply-delay as the latency behind it (comma list: one more axis of the grid; with "
+                         "--replay the word `list` takes the .npz file's occupancy and latency arrays)")
+    ap.add_argument("--write-reply-delay", type=int, default=None,
+                    help="closed loop, synthetic traffic: a write's latency at its memory node (default: --reply-delay)")
     ap.add_argument("--json", help="write the latency / throughput curve here")
     a = ap.parse_args(argv)
     a.rates_given = a.rates is not None

@@ -138,6 +138,10 @@ class RequestList:
     type: np.ndarray         # uint8 request type
     nodes: int               # nodes of the capturing network
     dropped: int = 0         # unanswered requests left out (unanswered="drop")
+    # optional, both or neither: uint32 cycles a request holds its memory node and the latency behind it
+    # (the memory point `list` of booksim.closed_loop_replay); a capture does not record them
+    occupancy: Optional[np.ndarray] = None
+    latency: Optional[np.ndarray] = None
 
     def __len__(self) -> int:
         return len(self.src)
@@ -209,11 +213,26 @@ def request_list(cap: Capture, timing: str = "captured", unanswered: str = "erro
                        q.type[keep].astype(np.uint8), cap.nodes, int(len(kq) - len(keep)))
 
 
-def save_request_npz(path: str, rl: RequestList) -> None:
+def save_request_npz(path: str, rl: RequestList, occupancy=None, latency=None) -> None:
     """A request list in the layout ``booksim --closed-loop --replay`` reads
-    (src, dst, bytes, reply_bytes, tinj), with ``nodes`` beside them."""
+    (src, dst, bytes, reply_bytes, tinj), with ``nodes`` beside them.  The
+    per-request ``occupancy`` and ``latency`` of the memory endpoint (the
+    arguments, else the list's own) are written when there are both."""
+    occupancy = rl.occupancy if occupancy is None else occupancy
+    latency = rl.latency if latency is None else latency
+    if (occupancy is None) != (latency is None):
+        raise ValueError("save_request_npz: occupancy and latency go together (one is missing)")
+    mem = {}
+    if occupancy is not None:
+        for name, a in (("occupancy", occupancy), ("latency", latency)):
+            a = np.asarray(a)
+            if a.shape != (len(rl),):
+                raise ValueError(f"save_request_npz: {name} has shape {a.shape}, the list has {len(rl)} requests")
+            if len(a) and int(a.min()) < 0:
+                raise ValueError(f"save_request_npz: {name} has a negative value")
+            mem[name] = a.astype(np.uint32)
     np.savez(path, src=rl.src, dst=rl.dst, bytes=rl.req_bytes, reply_bytes=rl.reply_bytes, tinj=rl.tcreate,
-             nodes=np.uint32(rl.nodes))
+             nodes=np.uint32(rl.nodes), **mem)
 
 
 def save_npz(path: str, cap: Capture, subnet: str = "request", flit_size: Optional[int] = None) -> None:

@@ -584,6 +584,15 @@ PYBIND11_MODULE(_asim, m) {
             else if (k == "max_outstanding") p.max_outstanding = py::cast<uint32_t>(v);
             else if (k == "batch_size") p.batch_size = py::cast<uint32_t>(v);
             else if (k == "batch_count") p.batch_count = py::cast<uint32_t>(v);
+            else if (k == "read_occupancy" || k == "write_occupancy" || k == "write_reply_delay") {
+              if (v.is_none()) continue;  // unset
+              const int64_t x = py::cast<int64_t>(v);
+              if (x < 0)
+                throw std::invalid_argument("icnt_closed_loop_batch: point " + std::to_string(ps.size()) + ": " + k +
+                                            " is negative (" + std::to_string(x) + ")");
+              if (k == "write_reply_delay") p.write_reply_delay = x;
+              else (k == "read_occupancy" ? p.read_occupancy : p.write_occupancy) = (uint32_t)std::min<int64_t>(x, 0xffffffffll);
+            }
             else throw std::invalid_argument("icnt_closed_loop_batch: point " + std::to_string(ps.size()) +
                                              ": unknown field '" + k + "'");
           }
@@ -625,6 +634,13 @@ PYBIND11_MODULE(_asim, m) {
           d["first_finish"] = r.first_finish;
           d["last_finish"] = r.last_finish;
           d["deadlocked"] = r.deadlocked;
+          d["mem_time"] = r.mem.mem_time;
+          d["max_mem_time"] = r.mem.max_mem_time;
+          d["mem_wait"] = r.mem.mem_wait;
+          d["mem_hold"] = r.mem.mem_hold;
+          d["mem_utilisation"] = r.mem.mem_utilisation;
+          d["max_mem_utilisation"] = r.mem.max_mem_utilisation;
+          d["mem_nodes_used"] = r.mem.mem_nodes_used;
           py::dict a;
           for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
           d["activity"] = a;
@@ -646,6 +662,7 @@ PYBIND11_MODULE(_asim, m) {
             d["request_arrivals"] = a64(r.request_arrivals);
             d["reply_arrivals"] = a64(r.reply_arrivals);
             d["state"] = a64(r.state);
+            d["reply_created"] = a64(r.reply_created);
           }
           out.append(d);
         }
@@ -658,7 +675,9 @@ PYBIND11_MODULE(_asim, m) {
       "doubled network.  A point is a dict with the fields of a request-reply point plus max_outstanding and either "
       "rate / cycles / warmup (the request list of icnt_request_reply_batch) or batch_size (every issuing node "
       "creates that many requests at cycle 0; batch_time is the last reply's arrival).  arrivals=True adds the "
-      "request list, tiss (issue times), request_arrivals, reply_arrivals (by request) and the state words.  "
+      "request list, tiss (issue times), request_arrivals, reply_arrivals (by request), the state words and "
+      "reply_created.  read_occupancy / write_occupancy / write_reply_delay turn the memory endpoint on (a memory node "
+      "is one server a request holds for its kind's occupancy, with reply_delay or write_reply_delay behind it).  "
       "ValueError names routing functions min_adapt / valiant, batch_count above 1 and mem_nodes that leave no "
       "issuer; step_cap is for tests and applies to every engine");
   m.def("icnt_cl_kernel_info", &icnt_cl_kernel_info, "registers, LDS and scratch of the closed-loop kernel");
@@ -666,7 +685,8 @@ PYBIND11_MODULE(_asim, m) {
       "icnt_closed_loop_networks",
       [](const py::tuple& list, const std::vector<std::string>& icnt_texts, const std::vector<uint32_t>& windows,
          uint64_t reply_delay, const std::string& engine, bool arrivals, uint64_t mem_budget_mb, uint64_t step_cap,
-         bool lds, uint32_t nodes) {
+         bool lds, uint32_t nodes, const py::object& occupancy, const py::object& latency,
+         const py::object& mem_points) {
         typedef py::array_t<uint32_t, py::array::c_style | py::array::forcecast> A32;
         typedef py::array_t<uint64_t, py::array::c_style | py::array::forcecast> A64;
         if (list.size() != 5)
@@ -686,6 +706,55 @@ PYBIND11_MODULE(_asim, m) {
         l.req_bytes.assign(q.data(), q.data() + std::min(cap, (size_t)q.size()));
         l.reply_bytes.assign(p.data(), p.data() + std::min(cap, (size_t)p.size()));
         l.tcreate.assign(tc.data(), tc.data() + std::min(cap, (size_t)tc.size()));
+        // the memory endpoint's arrays and points; a negative value names its argument
+        typedef py::array_t<int64_t, py::array::c_style | py::array::forcecast> AI64;
+        auto mem_array = [&](const py::object& o, const char* name, std::vector<uint32_t>& out) {
+          if (o.is_none()) return;
+          const AI64 a = AI64::ensure(o);
+          if (!a || a.ndim() != 1)
+            throw std::invalid_argument(std::string("icnt_closed_loop_networks: ") + name +
+                                        " must be a one-dimensional integer array");
+          const size_t n = std::min(cap, (size_t)a.size());
+          out.resize(n);
+          for (size_t i = 0; i < n; ++i) {
+            const int64_t x = a.data()[i];
+            if (x < 0)
+              throw std::invalid_argument(std::string("icnt_closed_loop_networks: ") + name + " of request " +
+                                          std::to_string(i) + " is negative (" + std::to_string(x) + ")");
+            out[i] = (uint32_t)std::min<int64_t>(x, 0xffffffffll);
+          }
+          if (!n && !l.src.empty())
+            throw std::invalid_argument(std::string("icnt_closed_loop_networks: ") + name + " has 0 entries, the list " +
+                                        std::to_string(l.src.size()));
+        };
+        mem_array(occupancy, "occupancy", l.occupancy);
+        mem_array(latency, "latency", l.latency);
+        if (occupancy.is_none() != latency.is_none())
+          throw std::invalid_argument(std::string("icnt_closed_loop_networks: ") +
+                                      (occupancy.is_none() ? "occupancy" : "latency") +
+                                      " is missing (give both arrays or neither)");
+        std::vector<ClosedLoopMemPoint> mps;
+        if (!mem_points.is_none()) {
+          for (const py::handle h : mem_points) {
+            ClosedLoopMemPoint mp;
+            const std::string at = "icnt_closed_loop_networks: mem_points[" + std::to_string(mps.size()) + "]";
+            if (py::isinstance<py::str>(h)) {
+              if (py::cast<std::string>(h) != "list")
+                throw std::invalid_argument(at + " is '" + py::cast<std::string>(h) + "': expected (occupancy, latency) or 'list'");
+              mp.list = true;
+            } else {
+              if (!py::isinstance<py::sequence>(h) || py::len(h) != 2)
+                throw std::invalid_argument(at + ": expected (occupancy, latency) or 'list'");
+              const py::sequence sq = py::reinterpret_borrow<py::sequence>(h);
+              const int64_t oc = py::cast<int64_t>(sq[0]), la = py::cast<int64_t>(sq[1]);
+              if (oc < 0 || la < 0) throw std::invalid_argument(at + " has a negative occupancy or latency");
+              mp.occupancy = (uint32_t)std::min<int64_t>(oc, 0xffffffffll);
+              mp.latency = (uint32_t)std::min<int64_t>(la, 0xffffffffll);
+            }
+            mps.push_back(mp);
+          }
+          if (mps.empty()) throw std::invalid_argument("icnt_closed_loop_networks: mem_points is empty (None: no memory axis)");
+        }
         OpenLoopBatchOpts o;
         o.arrivals = arrivals;
         o.mem_budget_mb = mem_budget_mb;
@@ -694,7 +763,7 @@ PYBIND11_MODULE(_asim, m) {
         std::vector<ClosedLoopNetResult> rs;
         {
           py::gil_scoped_release nogil;
-          rs = icnt_closed_loop_networks(l, icnt_texts, windows, reply_delay, engine, o);
+          rs = icnt_closed_loop_networks(l, icnt_texts, windows, reply_delay, engine, o, mps);
         }
         auto a32 = [](const std::vector<uint32_t>& v) { return py::array_t<uint32_t>((py::ssize_t)v.size(), v.data()); };
         auto a64 = [](const std::vector<uint64_t>& v) { return py::array_t<uint64_t>((py::ssize_t)v.size(), v.data()); };
@@ -724,6 +793,18 @@ PYBIND11_MODULE(_asim, m) {
           dd["first_finish"] = r.first_finish;
           dd["last_finish"] = r.last_finish;
           dd["deadlocked"] = r.deadlocked;
+          dd["mem_time"] = r.mem.mem_time;
+          dd["max_mem_time"] = r.mem.max_mem_time;
+          dd["mem_wait"] = r.mem.mem_wait;
+          dd["mem_hold"] = r.mem.mem_hold;
+          dd["mem_utilisation"] = r.mem.mem_utilisation;
+          dd["max_mem_utilisation"] = r.mem.max_mem_utilisation;
+          dd["mem_nodes_used"] = r.mem.mem_nodes_used;
+          if (r.mem_point >= 0) {
+            dd["mem_point"] = r.mem_point;
+            if (r.mem_list) dd["mem"] = "list";
+            else dd["mem"] = py::make_tuple(r.mem_occupancy, r.mem_latency);
+          }
           py::dict a;
           for (int i = 0; i < 7; ++i) a[an[i]] = r.activity[i];
           dd["activity"] = a;
@@ -742,6 +823,7 @@ PYBIND11_MODULE(_asim, m) {
             dd["request_arrivals"] = a64(r.request_arrivals);
             dd["reply_arrivals"] = a64(r.reply_arrivals);
             dd["state"] = a64(r.state);
+            dd["reply_created"] = a64(r.reply_created);
           }
           out.append(dd);
         }
@@ -749,14 +831,19 @@ PYBIND11_MODULE(_asim, m) {
       },
       py::arg("list"), py::arg("icnt_texts"), py::arg("windows"), py::arg("reply_delay") = 0, py::arg("engine") = "cpu",
       py::arg("arrivals") = false, py::arg("mem_budget_mb") = 0, py::arg("step_cap") = 0, py::arg("lds") = true,
-      py::kw_only(), py::arg("nodes") = 0,
+      py::kw_only(), py::arg("nodes") = 0, py::arg("occupancy") = py::none(), py::arg("latency") = py::none(),
+      py::arg("mem_points") = py::none(),
       "one request list (src, dst, req_bytes, reply_bytes, tcreate; tcreate non-decreasing) closed loop through many "
       "networks under many windows, one result per (.icnt text, window), network-major: every network derives both "
       "packets' flit counts from the bytes, a request's delivery creates its reply reply_delay cycles later and a "
       "node keeps at most `window` requests in flight (0: unlimited).  batch_time is the last reply's arrival.  "
       "nodes: the list's node count (0: not checked).  engine gpu: one wavefront per (network, window) in one launch "
       "(icnt_cln_sweep.hip).  arrivals=True adds tiss, request_arrivals, reply_arrivals, the network's flit counts "
-      "and the state words.  ValueError names the network of a bad entry; step_cap is for tests");
+      "and the state words.  mem_points: a third axis, each point (occupancy, latency) for every request or 'list' for the "
+      "per-request occupancy / latency arrays: a memory node is one server a request holds for its occupancy, with its "
+      "latency behind it, and replies leave a node in arrival order; results are network-major, then window, then memory "
+      "point, and carry mem_point / mem, mem_time, mem_wait, mem_hold, mem_utilisation (arrivals=True: reply_created).  "
+      "ValueError names the network of a bad entry or the bad argument; step_cap is for tests");
   m.def("icnt_closed_loop_networks_lds_bytes", &icnt_closed_loop_networks_lds_bytes, py::arg("icnt_texts"),
         "dynamic LDS (bytes) of one gpu launch over these networks: the largest 5 * U * V words among their doubled "
         "networks");

@@ -966,7 +966,21 @@ struct ClPoint {
   uint32_t issuers = 0;
   RtDims d{};                          // the doubled network's pass
   std::vector<uint32_t> src, dst, nfl;  // its 2 * nq packets
+  // the memory endpoint (model/icnt_closed.h rule 2m): CL_MEM_OFF, CL_MEM_ALL
+  // (occ_all / lat_all for every request) or CL_MEM_LIST (per request: the
+  // call's list's arrays, ext_*, else this point's own)
+  uint32_t mem = CL_MEM_OFF, occ_all = 0, lat_all = 0;
+  std::vector<uint32_t> occ, lat;
+  const std::vector<uint32_t>*ext_occ = nullptr, *ext_lat = nullptr;
+  int32_t mem_index = -1;  // of a many-networks call's memory points
 };
+
+const std::vector<uint32_t>* cl_occ(const ClPoint& pt) {
+  return pt.mem != CL_MEM_LIST ? nullptr : pt.ext_occ ? pt.ext_occ : &pt.occ;
+}
+const std::vector<uint32_t>* cl_lat(const ClPoint& pt) {
+  return pt.mem != CL_MEM_LIST ? nullptr : pt.ext_lat ? pt.ext_lat : &pt.lat;
+}
 
 ClPoint cl_prepare(const OpenLoopNet& net, const OpenLoopNet& dbl, const ClosedLoopParams& prm, size_t index) {
   const char* fn = "icnt_closed_loop_batch";
@@ -1018,6 +1032,24 @@ ClPoint cl_prepare(const OpenLoopNet& net, const OpenLoopNet& dbl, const ClosedL
   pt.writes = rr.writes;
   const uint32_t nq = pt.req.np;
   if (nq > kReplayMaxPackets / 2) throw std::invalid_argument(who + ": too many packets for one pass");
+  if (prm.read_occupancy || prm.write_occupancy || prm.write_reply_delay >= 0) {
+    const uint64_t wl = prm.write_reply_delay >= 0 ? (uint64_t)prm.write_reply_delay : prm.reply_delay;
+    auto fits = [&](uint64_t v, const char* key) {
+      if (v > kRtClMemMax)
+        throw std::invalid_argument(who + ": " + key + " " + std::to_string(v) + " is above 2^24 (the memory endpoint's limit)");
+    };
+    fits(prm.read_occupancy, "read_occupancy");
+    fits(prm.write_occupancy, "write_occupancy");
+    fits(prm.reply_delay, "reply_delay");
+    fits(wl, "write_reply_delay");
+    pt.mem = CL_MEM_LIST;
+    pt.occ.resize(nq);
+    pt.lat.resize(nq);
+    for (uint32_t i = 0; i < nq; ++i) {
+      pt.occ[i] = pt.kind[i] ? prm.write_occupancy : prm.read_occupancy;
+      pt.lat[i] = (uint32_t)(pt.kind[i] ? wl : prm.reply_delay);
+    }
+  }
   pt.src = pt.req.src;
   pt.dst = pt.req.dst;
   pt.nfl = pt.req.nfl;
@@ -1046,6 +1078,8 @@ ClUnit cl_unit(const ClPoint& pt) {
   u.dst = &pt.dst;
   u.nfl = &pt.nfl;
   u.tinj = &pt.req.tinj;
+  u.occ = cl_occ(pt);
+  u.lat = cl_lat(pt);
   return u;
 }
 
@@ -1062,8 +1096,19 @@ ClRaw cl_host(const OpenLoopNet& dbl, const ClPoint& pt, bool par, uint64_t step
   RtWork w;
   rt_carve(pt.d, scratch.data(), &w);
   RtClosed cl;
+  std::vector<uint32_t> svc;
   cl.window = pt.prm.max_outstanding;
   cl.delay = pt.prm.reply_delay;
+  if (pt.mem != CL_MEM_OFF) {
+    cl.mem = 1;
+    cl.occ_all = pt.occ_all;
+    cl.lat_all = pt.lat_all;
+    if (pt.mem == CL_MEM_LIST) {  // occupancies, then latencies
+      svc = *cl_occ(pt);
+      svc.insert(svc.end(), cl_lat(pt)->begin(), cl_lat(pt)->end());
+      cl.svc = svc.data();
+    }
+  }
   rt_cl_carve(pt.d, nq, scratch.data() + words, &cl);
   w.rt_off = dbl.rt_off.data();
   w.rt_links = dbl.rt_links.data();
@@ -1083,6 +1128,7 @@ ClRaw cl_host(const OpenLoopNet& dbl, const ClPoint& pt, bool par, uint64_t step
   }
   raw.pass.tarr.assign(w.tarr, w.tarr + 2 * (size_t)nq);
   raw.tiss.assign(cl.tiss, cl.tiss + nq);
+  if (cl.mem) raw.created.assign(w.tinj + nq, w.tinj + 2 * (size_t)nq);
   return raw;
 }
 
@@ -1103,6 +1149,12 @@ ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool
   const std::vector<uint64_t>&tarr = raw.pass.tarr, &tinj = pt.req.tinj;
   std::vector<uint64_t> finish(N, 0);
   std::vector<char> has(N, 0);
+  // the replies' creation times: the pass's with a memory endpoint
+  std::vector<uint64_t> created = std::move(raw.created);
+  if (pt.mem == CL_MEM_OFF) {
+    created.resize(nq);
+    for (uint32_t i = 0; i < nq; ++i) created[i] = tarr[i] + prm.reply_delay;
+  }
   double lq = 0, lp = 0, lr = 0, stall = 0, flight = 0;
   uint64_t last = 0, ej_req = 0, ej_rep = 0;
   for (uint32_t i = 0; i < nq; ++i) {
@@ -1118,7 +1170,7 @@ ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool
     if (!batch && tinj[i] < prm.warmup) continue;
     ++r.measured;
     lq += (double)(aq - ti);
-    lp += (double)(ap - (aq + prm.reply_delay));
+    lp += (double)(ap - created[i]);
     lr += (double)(ap - ti);
     stall += (double)(ti - tinj[i]);
     r.max_round_trip_latency = std::max(r.max_round_trip_latency, (double)(ap - ti));
@@ -1144,6 +1196,53 @@ ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool
     first = false;
   }
   r.avg_outstanding = active && last ? flight / ((double)active * (double)last) : 0;
+  {
+    // the memory endpoint, node by node in the order of the requests' arrivals
+    // (which strictly increase at a node): the server's recurrence once more
+    // for the service start and end, the creation times from the pass
+    const std::vector<uint32_t>*occ = cl_occ(pt), *lat = cl_lat(pt);
+    std::vector<uint32_t> order;
+    order.reserve(nq);
+    for (uint32_t i = 0; i < nq; ++i)
+      if (raw.tiss[i] != ~0ull && created[i] >= tarr[i]) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+      const uint32_t na = pt.req.dst[a], nb = pt.req.dst[b];
+      return na != nb ? na < nb : tarr[a] != tarr[b] ? tarr[a] < tarr[b] : a < b;
+    });
+    const double span = batch ? (double)std::max<uint64_t>(last, 1) : (double)(prm.cycles - prm.warmup);
+    double mt = 0, wait = 0, hold = 0, usum = 0, served = 0;
+    uint64_t busy = 0, count = 0;
+    for (size_t k = 0; k < order.size(); ++k) {
+      const uint32_t i = order[k], n = pt.req.dst[i];
+      if (!k || pt.req.dst[order[k - 1]] != n) {
+        busy = 0;
+        served = 0;
+      }
+      const uint64_t oc = pt.mem == CL_MEM_OFF ? 0 : occ ? (*occ)[i] : pt.occ_all;
+      const uint64_t la = pt.mem == CL_MEM_OFF ? prm.reply_delay : lat ? (*lat)[i] : pt.lat_all;
+      const uint64_t start = std::max(tarr[i], busy);
+      busy = start + oc;
+      if (batch || tinj[i] >= prm.warmup) {
+        ++count;
+        mt += (double)(created[i] - tarr[i]);
+        r.mem.max_mem_time = std::max(r.mem.max_mem_time, (double)(created[i] - tarr[i]));
+        wait += (double)(start - tarr[i]);
+        hold += (double)created[i] - (double)(busy + la);
+        served += (double)oc;
+      }
+      if (k + 1 == order.size() || pt.req.dst[order[k + 1]] != n) {
+        ++r.mem.mem_nodes_used;
+        usum += served / span;
+        r.mem.max_mem_utilisation = std::max(r.mem.max_mem_utilisation, served / span);
+      }
+    }
+    if (count) {
+      r.mem.mem_time = mt / count;
+      r.mem.mem_wait = wait / count;
+      r.mem.mem_hold = hold / count;
+    }
+    if (r.mem.mem_nodes_used) r.mem.mem_utilisation = usum / r.mem.mem_nodes_used;
+  }
   const NetEnergy e = net_energy(net, pt.d, raw.pass.act, last);
   r.e_buffer = e.buffer;
   r.e_xbar = e.xbar;
@@ -1161,6 +1260,7 @@ ClosedLoopResult cl_finish(const OpenLoopNet& net, ClPoint& pt, ClRaw& raw, bool
     r.request_flits = std::move(pt.req.nfl);
     r.request_tinj = std::move(pt.req.tinj);
     r.kind = std::move(pt.kind);
+    r.reply_created = std::move(created);
   }
   return r;
 }
@@ -1288,7 +1388,53 @@ ClnUnit cln_unit(const ClnNet& cn, const ClPoint& pt) {
   u.window = pt.prm.max_outstanding;
   u.delay = pt.prm.reply_delay;
   u.nfl = &pt.nfl;
+  u.mem = pt.mem;
+  u.occ = pt.occ_all;
+  u.lat = pt.lat_all;
   return u;
+}
+
+// what the call refuses of the memory endpoint's arguments, naming them
+void cln_check_mem(const ClosedLoopList& list, const std::vector<ClosedLoopMemPoint>& mem_points) {
+  const std::string who = "icnt_closed_loop_networks: ";
+  const size_t nq = list.src.size();
+  const bool has = !list.occupancy.empty() || !list.latency.empty();
+  if (has && list.occupancy.size() != nq)
+    throw std::invalid_argument(who + "occupancy has " + std::to_string(list.occupancy.size()) + " entries, the list " +
+                                std::to_string(nq));
+  if (has && list.latency.size() != nq)
+    throw std::invalid_argument(who + "latency has " + std::to_string(list.latency.size()) + " entries, the list " +
+                                std::to_string(nq));
+  for (size_t i = 0; has && i < nq; ++i) {
+    if (list.occupancy[i] > kRtClMemMax)
+      throw std::invalid_argument(who + "occupancy of request " + std::to_string(i) + " is above 2^24");
+    if (list.latency[i] > kRtClMemMax)
+      throw std::invalid_argument(who + "latency of request " + std::to_string(i) + " is above 2^24");
+  }
+  for (size_t m = 0; m < mem_points.size(); ++m) {
+    const ClosedLoopMemPoint& mp = mem_points[m];
+    if (mp.list && !has && nq)
+      throw std::invalid_argument(who + "mem_points[" + std::to_string(m) +
+                                  "] is `list`, but the list has no occupancy and latency arrays");
+    if (!mp.list && (mp.occupancy > kRtClMemMax || mp.latency > kRtClMemMax))
+      throw std::invalid_argument(who + "mem_points[" + std::to_string(m) + "] has an occupancy or latency above 2^24");
+  }
+}
+
+// memory point m of the call (none: rule 2's reply_delay) for a unit's point
+void cln_set_mem(ClPoint& pt, const ClosedLoopList& list, const std::vector<ClosedLoopMemPoint>& mem_points, size_t m) {
+  if (mem_points.empty()) return;
+  const ClosedLoopMemPoint& mp = mem_points[m];
+  pt.mem_index = (int32_t)m;
+  if (mp.list) {
+    pt.mem = CL_MEM_LIST;
+    pt.ext_occ = &list.occupancy;
+    pt.ext_lat = &list.latency;
+  } else {
+    pt.mem = CL_MEM_ALL;
+    pt.occ_all = mp.occupancy;
+    pt.lat_all = mp.latency;
+  }
 }
 
 ClosedLoopNetResult cln_finish(const ClnNet& cn, ClPoint& pt, ClRaw& raw, bool arrivals) {
@@ -1299,6 +1445,11 @@ ClosedLoopNetResult cln_finish(const ClnNet& cn, ClPoint& pt, ClRaw& raw, bool a
   ClosedLoopNetResult r;
   r.network = (uint32_t)cn.index;
   r.window = pt.prm.max_outstanding;
+  r.mem_point = pt.mem_index;
+  r.mem_list = pt.mem == CL_MEM_LIST;
+  r.mem_occupancy = pt.occ_all;
+  r.mem_latency = pt.mem == CL_MEM_ALL ? pt.lat_all : 0;
+  r.mem = c.mem;
   r.nodes = c.nodes;
   r.issuers = c.issuers;
   r.requests = c.requests;
@@ -1332,6 +1483,7 @@ ClosedLoopNetResult cln_finish(const ClnNet& cn, ClPoint& pt, ClRaw& raw, bool a
     r.request_arrivals = std::move(c.request_arrivals);
     r.reply_arrivals = std::move(c.reply_arrivals);
     r.state = std::move(c.state);
+    r.reply_created = std::move(c.reply_created);
   }
   return r;
 }
@@ -1341,41 +1493,51 @@ ClosedLoopNetResult cln_finish(const ClnNet& cn, ClPoint& pt, ClRaw& raw, bool a
 std::vector<ClosedLoopNetResult> icnt_closed_loop_networks(const ClosedLoopList& list,
                                                            const std::vector<std::string>& icnt_texts,
                                                            const std::vector<uint32_t>& windows, uint64_t reply_delay,
-                                                           const std::string& engine, const OpenLoopBatchOpts& opts) {
+                                                           const std::string& engine, const OpenLoopBatchOpts& opts,
+                                                           const std::vector<ClosedLoopMemPoint>& mem_points) {
   check_engine("icnt_closed_loop_networks", engine);
-  const size_t nw = windows.size();
+  cln_check_mem(list, mem_points);
+  const size_t nw = windows.size(), nm = std::max<size_t>(mem_points.size(), 1);
   std::vector<ClosedLoopNetResult> out;
-  out.reserve(icnt_texts.size() * nw);
+  out.reserve(icnt_texts.size() * nw * nm);
   g_last = OpenLoopBatchStats();
   if (engine != "gpu") {
     for (size_t i = 0; i < icnt_texts.size(); ++i) {
       const ClnNet cn = cln_prepare(list, icnt_texts[i], i, reply_delay);
-      for (uint32_t window : windows) {
-        ClPoint pt = cn.pt;
-        pt.prm.max_outstanding = window;
-        ClRaw raw = cl_host(cn.dbl, pt, engine == "cpu-par", opts.step_cap);
-        out.push_back(cln_finish(cn, pt, raw, opts.arrivals));
-      }
+      for (uint32_t window : windows)
+        for (size_t m = 0; m < nm; ++m) {
+          ClPoint pt = cn.pt;
+          pt.prm.max_outstanding = window;
+          cln_set_mem(pt, list, mem_points, m);
+          ClRaw raw = cl_host(cn.dbl, pt, engine == "cpu-par", opts.step_cap);
+          out.push_back(cln_finish(cn, pt, raw, opts.arrivals));
+        }
     }
     return out;
   }
-  // gpu: the (network, window) units are prepared one after the other,
-  // network-major, and packed into chunks under the memory budget (the list's
+  // gpu: the (network, window, memory point) units are prepared one after the
+  // other, network-major, and packed into chunks under the memory budget (the list's
   // device copy counts once per chunk, a network's tables once per unit); a
   // full chunk is one launch
   struct Item {
     std::shared_ptr<const ClnNet> cn;
     ClPoint pt;
   };
-  const ClList cl{&list.src, &list.dst, &list.req_bytes, &list.reply_bytes, &list.tcreate};
+  ClList cl{&list.src, &list.dst, &list.req_bytes, &list.reply_bytes, &list.tcreate};
+  for (const ClosedLoopMemPoint& mp : mem_points)
+    if (mp.list && !list.occupancy.empty()) {  // uploaded with the list, once per chunk
+      cl.occ = &list.occupancy;
+      cl.lat = &list.latency;
+    }
   std::shared_ptr<const ClnNet> cur;
   pack_chunks<Item, ClRaw>(
-      "icnt_closed_loop_networks: unit", opts, icnt_cln_list_bytes(cl), icnt_texts.size() * nw,
+      "icnt_closed_loop_networks: unit", opts, icnt_cln_list_bytes(cl), icnt_texts.size() * nw * nm,
       [&](size_t i) {
-        const size_t ni = i / nw;
+        const size_t ni = i / (nw * nm);
         if (!cur || cur->index != ni) cur = std::make_shared<const ClnNet>(cln_prepare(list, icnt_texts[ni], ni, reply_delay));
         Item it{cur, cur->pt};
-        it.pt.prm.max_outstanding = windows[i % nw];
+        it.pt.prm.max_outstanding = windows[i / nm % nw];
+        cln_set_mem(it.pt, list, mem_points, i % nm);
         return it;
       },
       [](const Item& it) { return icnt_cln_unit_bytes(cln_unit(*it.cn, it.pt)); },

@@ -211,6 +211,12 @@ std::vector<RequestReplyResult> icnt_request_reply_batch(const std::string& icnt
 //          the same fields; with max_outstanding 0 the point is that point
 //   batch  every issuing node creates batch_size requests at cycle 0,
 //          destinations from the pattern, kinds from write_fraction
+// The memory endpoint (model/icnt_closed.h rule 2m): with read_occupancy,
+// write_occupancy or write_reply_delay set, a memory node is one server that a
+// read holds for read_occupancy cycles and a write for write_occupancy, with
+// reply_delay (a write: write_reply_delay) cycles of pipelined latency behind
+// it, and replies leave a node in the order their requests arrived.  With all
+// three unset the reply is created reply_delay after the arrival, as before.
 struct ClosedLoopParams {
   std::string traffic = "uniform";
   uint64_t seed = 1;
@@ -223,6 +229,20 @@ struct ClosedLoopParams {
   uint64_t cycles = 2000, warmup = 500;
   uint32_t batch_size = 0;   // > 0: a batch point
   uint32_t batch_count = 1;  // only 1 is modelled
+  uint32_t read_occupancy = 0, write_occupancy = 0;  // cycles a request holds its memory node
+  int64_t write_reply_delay = -1;                    // a write's latency; < 0: reply_delay
+};
+
+// what the memory endpoint did to a point, over the measured requests (the
+// model off: mem_time = reply_delay, the rest 0)
+struct ClosedLoopMemStats {
+  double mem_time = 0, max_mem_time = 0;  // reply creation - request arrival
+  double mem_wait = 0;                    // service start - arrival: the queue in front of the server
+  double mem_hold = 0;                    // creation - (service end + latency): the in-order return
+  // a node's summed occupancy over the batch time (rate points: the measured
+  // requests' over the measurement window), over the nodes that served a request
+  double mem_utilisation = 0, max_mem_utilisation = 0;
+  uint32_t mem_nodes_used = 0;
 };
 
 struct ClosedLoopResult {
@@ -244,6 +264,8 @@ struct ClosedLoopResult {
   // both arrival arrays by request, the doubled network's state words
   std::vector<uint32_t> request_src, request_dst, request_flits, kind;
   std::vector<uint64_t> request_tinj, tiss, request_arrivals, reply_arrivals, state;
+  ClosedLoopMemStats mem;
+  std::vector<uint64_t> reply_created;  // on request: every reply's creation time
 };
 
 // every point through one engine: "cpu" (rt_simulate_closed), "cpu-par"
@@ -266,11 +288,20 @@ std::vector<ClosedLoopResult> icnt_closed_loop_batch(const std::string& icnt_tex
 // from src[i] to dst[i] with req_bytes[i] bytes, is created at tcreate[i]
 // (non-decreasing, so a node's requests are in issue order) and is answered
 // by a reply of reply_bytes[i] bytes.  nodes: the node count the list was made
-// for (0: unknown)
+// for (0: unknown).  occupancy / latency: optional, both or neither, the
+// memory endpoint's per-request cycles for the memory point `list`
 struct ClosedLoopList {
   uint32_t nodes = 0;
   std::vector<uint32_t> src, dst, req_bytes, reply_bytes;
   std::vector<uint64_t> tcreate;
+  std::vector<uint32_t> occupancy, latency;
+};
+
+// a point of the memory axis: (occupancy, latency) for every request, or the
+// list's own arrays
+struct ClosedLoopMemPoint {
+  bool list = false;
+  uint32_t occupancy = 0, latency = 0;
 };
 
 // a (network, window) point: every request is measured (as for a batch point
@@ -279,6 +310,10 @@ struct ClosedLoopList {
 // of them in flight
 struct ClosedLoopNetResult {
   uint32_t network = 0, window = 0;  // index into icnt_texts; 0: unlimited
+  // the memory point: its index into mem_points (-1: the call had none), and the point
+  int32_t mem_point = -1;
+  bool mem_list = false;
+  uint32_t mem_occupancy = 0, mem_latency = 0;
   uint32_t nodes = 0, issuers = 0;
   uint64_t requests = 0, measured = 0;
   uint64_t request_flits = 0, reply_flits = 0;  // the list's totals on this network
@@ -295,11 +330,16 @@ struct ClosedLoopNetResult {
   // arrays by request, this network's flit counts, the doubled network's state words
   std::vector<uint32_t> request_flit_counts, reply_flit_counts;
   std::vector<uint64_t> tiss, request_arrivals, reply_arrivals, state;
+  ClosedLoopMemStats mem;
+  std::vector<uint64_t> reply_created;  // on request: every reply's creation time
 };
 
 // the list through every network of icnt_texts under every window of
 // `windows`, one closed-loop pass each (model/icnt_closed.h) on the network's
-// doubled network; one result per (network, window), network-major.  Network i
+// doubled network; one result per (network, window), network-major.  With
+// mem_points every (network, window) also runs under every memory point
+// (model/icnt_closed.h rule 2m), network-major, then window, then memory
+// point; without, reply_delay answers every request as before.  Network i
 // carries both packets of a request with
 //   flits = min(rt_flits(c_i, bytes), rt_flits(c_i, kRtMaxPktBytes))
 // (model/icnt_closed.h rt_cl_fill_list).  "cpu" is the defining form, a loop
@@ -308,14 +348,17 @@ struct ClosedLoopNetResult {
 // the memory budget takes (engine/icnt_cln_sweep.hip).  std::invalid_argument,
 // naming the network: a node count other than list.nodes (when it states one),
 // src == dst or a node out of range, a decreasing tcreate, arrays of unequal
-// length, more than kReplayMaxPackets / 2 requests, and what
+// length (occupancy and latency included), an occupancy or latency above
+// kRtClMemMax = 2^24, the memory point `list` without both arrays, more than
+// kReplayMaxPackets / 2 requests, and what
 // icnt_closed_loop_batch refuses of a network; std::runtime_error: a pass cut
 // off by its loop guard (opts.step_cap applies to every engine).
 std::vector<ClosedLoopNetResult> icnt_closed_loop_networks(const ClosedLoopList& list,
                                                            const std::vector<std::string>& icnt_texts,
                                                            const std::vector<uint32_t>& windows,
                                                            uint64_t reply_delay = 0, const std::string& engine = "cpu",
-                                                           const OpenLoopBatchOpts& opts = OpenLoopBatchOpts());
+                                                           const OpenLoopBatchOpts& opts = OpenLoopBatchOpts(),
+                                                           const std::vector<ClosedLoopMemPoint>& mem_points = {});
 
 // the dynamic LDS (bytes) one gpu launch over these networks takes for the
 // per-(unit, VC) words: the largest 5 * U * V words among their doubled

@@ -39,6 +39,10 @@ __global__ __launch_bounds__(64) void icnt_cl_kernel(const SimCfg* cfg, const Cl
   RtClosed cl;
   cl.window = pt.window;
   cl.delay = pt.delay;
+  if (pt.svc_off) {  // the memory endpoint (0: rule 2's reply_delay)
+    cl.mem = 1;
+    cl.svc = reinterpret_cast<const uint32_t*>(base + pt.svc_off);
+  }
   rt_cl_carve(pt.d, pt.nq, reinterpret_cast<uint32_t*>(base + pt.cl_off), &cl);
   sweep_pass_closed(*cfg, pt.d, reinterpret_cast<uint64_t*>(base + pt.st_off), w, cl, outs + blockIdx.x, step_cap,
                     hot_lds, hot_words);
@@ -73,6 +77,11 @@ void check_unit(const OpenLoopNet& net, const ClUnit& u) {
   const size_t n2 = 2 * (size_t)u.nq;
   if (u.src->size() != n2 || u.dst->size() != n2 || u.nfl->size() != n2 || u.tinj->size() != u.nq)
     bad("a unit's arrays differ in length");
+  if (!u.occ != !u.lat || (u.occ && (u.occ->size() != u.nq || u.lat->size() != u.nq)))
+    bad("a unit's occupancy and latency arrays differ in length from its requests");
+  if (u.occ)
+    for (uint32_t i = 0; i < u.nq; ++i)
+      if ((*u.occ)[i] > kRtClMemMax || (*u.lat)[i] > kRtClMemMax) bad("a unit's occupancy or latency is above 2^24");
   if (d.N != net.N || d.N % 2 || d.L != net.an_L || d.U != d.N + d.L || d.H != net.an_H || !d.V || !d.B)
     bad("a unit's network is not the chunk's");
   const uint32_t n = d.N / 2;
@@ -127,6 +136,10 @@ bool icnt_cl_run_chunk(const OpenLoopNet& net, const std::vector<ClUnit>& units,
     ch.up(dw[i].dst, u.dst->data(), n2 * 4);
     ch.up(dw[i].nfl, u.nfl->data(), n2 * 4);
     ch.up(dw[i].tinj, u.tinj->data(), (size_t)u.nq * 8);  // (the replies' are written by the pass)
+    if (u.occ) {
+      ch.up(h_pts[i].svc_off, u.occ->data(), (size_t)u.nq * 4);
+      ch.up(h_pts[i].svc_off + (uint64_t)u.nq * 4, u.lat->data(), (size_t)u.nq * 4);
+    }
   }
   hipLaunchKernelGGL(icnt_cl_kernel, dim3((unsigned)n), dim3(64), hot_lds ? (size_t)hot_bytes : 0, 0,
                      ch.at<const SimCfg>(o_net.cfg), ch.at<const ClPt>(l.o_pts), ch.at<SweepOut>(l.o_out), ch.base(),
@@ -137,6 +150,10 @@ bool icnt_cl_run_chunk(const OpenLoopNet& net, const std::vector<ClUnit>& units,
     ch.fetch_raw(raws[i].pass, outs[i], h_pts[i].d, h_pts[i].st_off, dw[i].tarr, 2 * nq);
     raws[i].tiss.assign(nq, 0);
     ch.down(raws[i].tiss.data(), dc[i].tiss, nq * 8);
+    if (units[i].occ) {
+      raws[i].created.assign(nq, 0);
+      ch.down(raws[i].created.data(), dw[i].tinj + nq, nq * 8);
+    }
   }
   return hot_lds;
 }

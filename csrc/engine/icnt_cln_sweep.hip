@@ -11,7 +11,10 @@
 // (rt_cl_fill_list), deriving both packets' flits from their bytes with that
 // unit's flit size:
 //   nfl = min(rt_flits(c, bytes), rt_flits(c, kRtMaxPktBytes))
-// (the host computed the same numbers to size and bound the unit).
+// (the host computed the same numbers to size and bound the unit).  The memory
+// endpoint's per-request occupancy and latency arrays, when the list has them,
+// are uploaded with it; a unit reads them (CL_MEM_LIST), uses its descriptor's
+// two scalars for every request (CL_MEM_ALL) or takes rule 2's reply_delay.
 //
 // The per-(unit, VC) words go in LDS under the kIcntSweepLdsBytes rule, applied
 // to the LARGEST 5 * U * V words among the chunk's doubled networks, for which
@@ -37,7 +40,8 @@ namespace asim {
 __global__ __launch_bounds__(64) void icnt_cln_kernel(const ClNetPt* pts, SweepOut* outs, char* base,
                                                       const uint32_t* l_src, const uint32_t* l_dst,
                                                       const uint32_t* l_req_bytes, const uint32_t* l_reply_bytes,
-                                                      const uint64_t* l_tcreate, uint64_t step_cap, int hot_lds) {
+                                                      const uint64_t* l_tcreate, const uint32_t* l_svc,
+                                                      uint64_t step_cap, int hot_lds) {
   extern __shared__ uint32_t hot_words[];  // hot_lds: the chunk's largest 5 * U * V words (the host sized the launch)
   const ClNetPt pt = pts[blockIdx.x];
   if (!pt.nq) return;  // (the chunk was cleared: no activity, nothing lost, status OK)
@@ -53,6 +57,12 @@ __global__ __launch_bounds__(64) void icnt_cln_kernel(const ClNetPt* pts, SweepO
   RtClosed cl;
   cl.window = pt.window;
   cl.delay = pt.delay;
+  if (pt.mem != CL_MEM_OFF) {
+    cl.mem = 1;
+    cl.occ_all = pt.occ;
+    cl.lat_all = pt.lat;
+    if (pt.mem == CL_MEM_LIST) cl.svc = l_svc;
+  }
   rt_cl_carve(pt.d, pt.nq, reinterpret_cast<uint32_t*>(base + pt.cl_off), &cl);
   // this network's packets from the shared list
   RtClList l;
@@ -80,6 +90,12 @@ void check_list(const ClList& l) {
   for (size_t i = 1; i < n; ++i)
     if ((*l.tcreate)[i] < (*l.tcreate)[i - 1])
       throw std::invalid_argument("icnt closed-loop network sweep: the requests are not in time order");
+  if (!l.occ != !l.lat || (l.occ && (l.occ->size() != n || l.lat->size() != n)))
+    throw std::invalid_argument("icnt closed-loop network sweep: the occupancy and latency arrays differ in length from the list");
+  if (l.occ)
+    for (size_t i = 0; i < n; ++i)
+      if ((*l.occ)[i] > kRtClMemMax || (*l.lat)[i] > kRtClMemMax)
+        throw std::invalid_argument("icnt closed-loop network sweep: an occupancy or latency is above 2^24");
 }
 
 // std::invalid_argument unless everything the kernel will index lies inside
@@ -96,6 +112,8 @@ void check_unit(const ClList& l, const ClnUnit& u, size_t index, bool tables) {
   const size_t nq = l.src->size();
   if (u.nq != nq || 2 * nq > d.np) bad("packets exceed its dimensions");
   if (u.nfl->size() != 2 * nq) bad("flit counts differ in length");
+  if (u.mem > CL_MEM_LIST || (u.mem == CL_MEM_LIST && !l.occ)) bad("memory point needs the list's occupancy and latency");
+  if (u.mem == CL_MEM_ALL && (u.occ > kRtClMemMax || u.lat > kRtClMemMax)) bad("occupancy or latency is above 2^24");
   if (!net.anynet || d.N != net.N || d.N % 2 || d.L != net.an_L || d.U != d.N + d.L || d.H != net.an_H || !d.V ||
       !d.B || !d.H)
     bad("dimensions are not its doubled network's");
@@ -141,7 +159,7 @@ bool icnt_cln_run_chunk(const ClList& list, const std::vector<ClnUnit>& units, u
   const size_t nq = list.src->size();
   ChunkLayout l;
   l.records<ClNetPt>(n);
-  const ClListOff o_list = place_cl_list(l, nq);
+  const ClListOff o_list = place_cl_list(l, nq, list.occ != nullptr);
   std::vector<ClNetPt> h_pts(n);
   uint64_t accounted = icnt_cln_list_bytes(list);
   for (size_t i = 0; i < n; ++i) {
@@ -159,20 +177,29 @@ bool icnt_cln_run_chunk(const ClList& list, const std::vector<ClnUnit>& units, u
   ch.up(o_list.req.bytes, list.req_bytes->data(), nq * 4);
   ch.up(o_list.req.tinj, list.tcreate->data(), nq * 8);
   ch.up(o_list.reply_bytes, list.reply_bytes->data(), nq * 4);
+  if (list.occ) {
+    ch.up(o_list.svc, list.occ->data(), nq * 4);
+    ch.up(o_list.svc + nq * 4, list.lat->data(), nq * 4);
+  }
   for (size_t i = 0; i < n; ++i) ch.up_net(h_pts[i].net, *units[i].dbl);  // (empty latency tables: nothing is copied)
   hipLaunchKernelGGL(icnt_cln_kernel, dim3((unsigned)n), dim3(64), hot_lds ? (size_t)hot_bytes : 0, 0,
                      ch.at<const ClNetPt>(l.o_pts), ch.at<SweepOut>(l.o_out), ch.base(),
                      ch.at<const uint32_t>(o_list.req.src), ch.at<const uint32_t>(o_list.req.dst),
                      ch.at<const uint32_t>(o_list.req.bytes), ch.at<const uint32_t>(o_list.reply_bytes),
-                     ch.at<const uint64_t>(o_list.req.tinj), step_cap, hot_lds ? 1 : 0);
+                     ch.at<const uint64_t>(o_list.req.tinj), ch.at<const uint32_t>(o_list.svc),
+                     step_cap, hot_lds ? 1 : 0);
   const std::vector<SweepOut> outs = ch.finish(n, l.o_out);
   for (size_t i = 0; i < n; ++i) {
-    ch.fetch_raw(raws[i].pass, outs[i], h_pts[i].d, h_pts[i].st_off,
-                 device_work(ch, h_pts[i].d, h_pts[i].scr_off).tarr, 2 * nq);
+    const RtWork dw = device_work(ch, h_pts[i].d, h_pts[i].scr_off);
+    ch.fetch_raw(raws[i].pass, outs[i], h_pts[i].d, h_pts[i].st_off, dw.tarr, 2 * nq);
     RtClosed dc;
     rt_cl_carve(h_pts[i].d, (uint32_t)nq, ch.at<uint32_t>(h_pts[i].cl_off), &dc);
     raws[i].tiss.assign(nq, 0);
     ch.down(raws[i].tiss.data(), dc.tiss, nq * 8);
+    if (units[i].mem != CL_MEM_OFF) {
+      raws[i].created.assign(nq, 0);
+      ch.down(raws[i].created.data(), dw.tinj + nq, nq * 8);
+    }
   }
   return hot_lds;
 }

@@ -120,12 +120,19 @@ struct ClUnit {
   uint64_t delay = 0;
   const std::vector<uint32_t>*src = nullptr, *dst = nullptr, *nfl = nullptr;  // 2 * nq each
   const std::vector<uint64_t>* tinj = nullptr;                               // nq
+  // the memory endpoint (model/icnt_closed.h rule 2m): both null, rule 2's
+  // `delay`; else every request's occupancy and latency, nq each
+  const std::vector<uint32_t>*occ = nullptr, *lat = nullptr;
 };
 
-// what a unit leaves: the pass (tarr of the 2 * nq packets) and the issue times
+// the memory endpoint of a many-networks unit
+enum ClMem : uint32_t { CL_MEM_OFF = 0, CL_MEM_ALL = 1, CL_MEM_LIST = 2 };
+
+// what a unit leaves: the pass (tarr of the 2 * nq packets), the issue times
+// and, with a memory endpoint, the replies' creation times
 struct ClRaw {
   OpenLoopRaw pass;
-  std::vector<uint64_t> tiss;
+  std::vector<uint64_t> tiss, created;
 };
 
 // one launch over the doubled network `net` (tables, `lat` / `inj_lat` empty
@@ -144,9 +151,12 @@ std::map<std::string, uint64_t> icnt_cl_kernel_info();
 struct ClList {
   const std::vector<uint32_t>*src = nullptr, *dst = nullptr, *req_bytes = nullptr, *reply_bytes = nullptr;
   const std::vector<uint64_t>* tcreate = nullptr;
+  // optional, both or neither: per-request occupancy and latency of the
+  // memory endpoint, for the units with mem == CL_MEM_LIST
+  const std::vector<uint32_t>*occ = nullptr, *lat = nullptr;
 };
 
-// one unit of a launch: a (network, window) point.  dbl: the network's doubled
+// one unit of a launch: a (network, window, memory point).  dbl: the network's doubled
 // network (tables; `lat` / `inj_lat` empty for the uniform channel latency),
 // which the unit places for itself; nfl: the 2 * nq flit counts the host
 // derived, which the device must reproduce
@@ -156,6 +166,8 @@ struct ClnUnit {
   uint32_t nq = 0, window = 0;
   uint64_t delay = 0;
   const std::vector<uint32_t>* nfl = nullptr;
+  // CL_MEM_OFF: `delay`; CL_MEM_ALL: occ / lat for every request; CL_MEM_LIST: the list's arrays
+  uint32_t mem = CL_MEM_OFF, occ = 0, lat = 0;
 };
 
 // the dynamic LDS of a chunk's launch: the largest 5 * U * V words among its

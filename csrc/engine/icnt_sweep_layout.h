@@ -72,8 +72,9 @@ struct alignas(16) ClPt {  // a closed-loop point on the doubled network
   uint32_t nq, window;
   uint64_t delay;
   uint64_t st_off, scr_off, cl_off;  // cl: rt_cl_carve(d, nq)
+  uint64_t svc_off;                  // the memory endpoint's 2 * nq words (occupancies, latencies); 0 (never a unit's offset): off
 };
-// a closed-loop unit of a many-networks chunk: one (network, window) point on
+// a closed-loop unit of a many-networks chunk: one (network, window, memory point) on
 // its own doubled network.  net: the unit's SimCfg and doubled route tables;
 // net.lat / net.ilat 0 (the descriptors' offset, never a table's): the
 // uniform channel latency
@@ -83,6 +84,7 @@ struct alignas(16) ClNetPt {
   uint64_t delay;
   NetOff net;
   uint64_t st_off, scr_off, cl_off;  // cl: rt_cl_carve(d, nq)
+  uint32_t mem, occ, lat, pad_;      // ClMem; CL_MEM_ALL: every request's occupancy and latency
 };
 struct ListOff {  // the shared list of a many-networks chunk
   uint64_t src, dst, bytes, tinj;
@@ -90,6 +92,7 @@ struct ListOff {  // the shared list of a many-networks chunk
 struct ClListOff {  // the shared request list of a closed-loop many-networks chunk
   ListOff req;      // src, dst, request bytes, creation times
   uint64_t reply_bytes;
+  uint64_t svc;  // the memory endpoint's occupancies, then latencies (no bytes when the list has none)
 };
 static_assert(sizeof(SweepOut) % 16 == 0 && sizeof(SweepPt) % 16 == 0 && sizeof(RrPt) % 16 == 0 &&
                   sizeof(NetPt) % 16 == 0 && sizeof(ClPt) % 16 == 0 && sizeof(ClNetPt) % 16 == 0,
@@ -116,10 +119,11 @@ inline ListOff place_list(ChunkLayout& l, uint64_t np) {
   return o;
 }
 
-inline ClListOff place_cl_list(ChunkLayout& l, uint64_t nq) {
+inline ClListOff place_cl_list(ChunkLayout& l, uint64_t nq, bool mem) {
   ClListOff o;
   o.req = place_list(l, nq);
   o.reply_bytes = l.take(nq * 4);
+  o.svc = l.take(mem ? 2 * nq * 4 : 0);
   return o;
 }
 
@@ -171,6 +175,7 @@ inline ClPt place_cl_unit(ChunkLayout& l, const ClUnit& u) {
   h.delay = u.delay;
   place_pass(l, h.d, h.st_off, h.scr_off);
   h.cl_off = l.take(rt_cl_carve(h.d, h.nq, nullptr, nullptr) * 4);
+  if (u.occ) h.svc_off = l.take(2ull * h.nq * 4);
   return h;
 }
 
@@ -180,6 +185,9 @@ inline ClNetPt place_cln_unit(ChunkLayout& l, const ClnUnit& u) {
   h.nq = u.nq;
   h.window = u.window;
   h.delay = u.delay;
+  h.mem = u.mem;
+  h.occ = u.occ;
+  h.lat = u.lat;
   h.net = place_net(l, *u.dbl);
   if (u.dbl->lat.empty()) h.net.lat = h.net.ilat = 0;
   place_pass(l, h.d, h.st_off, h.scr_off);
@@ -203,7 +211,7 @@ inline uint64_t icnt_net_list_bytes(const NetList& list) {
 }
 inline uint64_t icnt_cln_list_bytes(const ClList& list) {
   ChunkLayout l;
-  place_cl_list(l, list.src ? list.src->size() : 0);
+  place_cl_list(l, list.src ? list.src->size() : 0, list.occ != nullptr);
   return l.bytes;
 }
 

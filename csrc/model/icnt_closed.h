@@ -31,6 +31,27 @@
 //     the tail of node N + dst's source queue.  Arrivals at a node come over
 //     its one ejection link and strictly increase, so the tail append keeps
 //     the queue in (time, packet) order.
+//  2m. Reply creation with a memory endpoint (cl.mem set; rt_cl_delivered).
+//     The memory node n = N + dst is one server, first come first served, with
+//     a pipelined latency behind it.  Request i holds the server for occ[i]
+//     cycles and its reply leaves lat[i] cycles after the server is done:
+//       start   = max(arr, busy[n])
+//       busy[n] = start + occ[i]
+//       ready   = busy[n] + lat[i]
+//       tinj    = ready                    if n created no reply yet
+//                 max(ready, last[n] + 1)  otherwise
+//       last[n] = tinj
+//     busy[n] starts at 0.  The last line is a modelling choice: replies leave
+//     a node in the order their requests arrived, so a fast reply can be held
+//     one cycle behind a slow older one (the cycle simulation's L2 returns
+//     replies in completion order).  It keeps a node's creation times strictly
+//     increasing when latencies differ, so the tail append still keeps the
+//     queue in (time, packet) order and the source-list key, source_time and
+//     the next-event scan need no sorted insert.  With occ = 0 and lat = delay
+//     for every request this is rule 2: a node's arrivals strictly increase,
+//     so busy never exceeds arr and the hold never binds.  occ and lat are
+//     read-only inputs (svc: [nq] each, or one pair of scalars for every request);
+//     busy[n] and last[n] belong to the lane of the packet delivered at n.
 //  3. Release (rt_cl_delivered, a reply).  The reply's arrival is queued on
 //     its requester's release list, in time order for the same reason, and
 //     applied by the gate at the top of the cycle it falls due.
@@ -52,10 +73,17 @@
 // Events: besides the sources', units' and credits' times the next-event scan
 // sees rt_cl_gate_time: the creation time of a node's next request while its
 // gate is open, its earliest queued release while it is closed.  These add at
-// most 2 * nq event times to a pass (rt_cl_step_cap).
+// most 2 * nq event times to a pass (rt_cl_step_cap).  A memory endpoint adds
+// none: it moves a reply's creation time, which is the source event of that
+// packet already counted among the injections, and a pass still ends no later
+// than after one event per counted item.
 #pragma once
 
 namespace asim {
+
+// the largest occupancy and latency of rule 2m: the times of the 25 million
+// requests a pass may hold stay far inside 64 bits
+constexpr uint32_t kRtClMemMax = 1u << 24;
 
 // parameters and work arrays of a closed-loop pass; d.N is the doubled network's
 struct RtClosed {
@@ -68,6 +96,13 @@ struct RtClosed {
   // outstanding, packets still to inject, the first packet ever queued
   uint32_t *ghead = nullptr, *gtail = nullptr, *rhead = nullptr, *rtail = nullptr, *out = nullptr, *left = nullptr,
            *sfirst = nullptr;
+  // rule 2m (mem 0: rule 2, nothing below is read)
+  uint32_t mem = 0;
+  uint32_t occ_all = 0, lat_all = 0;  // every request's, when svc is null
+  // [2 * nq] per request, read only (not carved): occ[i] = svc[i], lat[i] = svc[nq + i]
+  const uint32_t* svc = nullptr;
+  // [2 * d.N] node n's busy (the server is free from) and last (the last creation, ~0: none) at 2 * n, 2 * n + 1
+  uint64_t* node = nullptr;
 };
 
 // carve the closed-loop arrays out of `base` (nullptr: size only); u32 words
@@ -81,6 +116,7 @@ SIM_HDI uint64_t rt_cl_carve(const RtDims& d, uint32_t nq, uint32_t* base, RtClo
   RtClosed t = cl ? *cl : RtClosed();
   t.nq = nq;
   t.tiss = reinterpret_cast<uint64_t*>(take32(2ull * nq));  // (base is 8-byte aligned)
+  t.node = reinterpret_cast<uint64_t*>(take32(4ull * d.N));
   t.gnext = take32(nq);
   t.rnext = take32(nq);
   t.ghead = take32(d.N);
@@ -155,6 +191,10 @@ SIM_HDI void rt_cl_setup(const CX& cx, const RtClosed& cl, uint32_t& nsrc) {
   for (uint32_t s = 0; s < cx.N; ++s) {
     cl.ghead[s] = cl.gtail[s] = cl.rhead[s] = cl.rtail[s] = cl.sfirst[s] = kRtNone;
     cl.out[s] = cl.left[s] = 0;
+    if (cl.mem) {
+      cl.node[2 * s] = 0;
+      cl.node[2 * s + 1] = ~0ull;
+    }
   }
   for (uint32_t i = 0; i < cl.nq; ++i) {
     const uint32_t s = w.src[i];
@@ -205,16 +245,30 @@ SIM_HDI bool rt_cl_listed(const RtClosed& cl, uint32_t s) { return cl.left[s] !=
 // source s injected the last flit of a packet
 SIM_HDI void rt_cl_injected(const RtClosed& cl, uint32_t s) { --cl.left[s]; }
 
+// rule 2m: the creation time of the reply of request i, delivered at memory
+// node n with arrival arr
+SIM_HDI uint64_t rt_cl_mem_serve(const RtClosed& cl, uint32_t i, uint32_t n, uint64_t arr) {
+  const uint64_t oc = cl.svc ? cl.svc[i] : cl.occ_all, la = cl.svc ? cl.svc[cl.nq + i] : cl.lat_all;
+  uint64_t* w = cl.node + 2 * (uint64_t)n;
+  const uint64_t b = w[0], done = (arr > b ? arr : b) + oc, last = w[1];
+  uint64_t t = done + la;
+  if (last != ~0ull && t <= last) t = last + 1;
+  w[0] = done;
+  w[1] = t;
+  return t;
+}
+
 // rules 2 and 3: the tail of packet p was delivered (w.tarr[p] is set).
 // Returns the reply node that queued its first packet and is to be listed
 // (rt_cl_list_source), else kRtNone.  Two packets delivered in one switch pass
-// arrive at different nodes, so they touch different queues and lists.
+// arrive at different nodes, so they touch different queues, lists and
+// memory-endpoint words.
 template <class CX>
 SIM_HDI uint32_t rt_cl_delivered(const CX& cx, const RtClosed& cl, uint32_t p) {
   const RtWork& w = cx.w;
   if (p < cl.nq) {
     const uint32_t q = cl.nq + p, n = w.src[q];
-    w.tinj[q] = w.tarr[p] + cl.delay;
+    w.tinj[q] = cl.mem ? rt_cl_mem_serve(cl, p, n, w.tarr[p]) : w.tarr[p] + cl.delay;
     rt_cl_enqueue(w, n, q);
     if (cl.sfirst[n] != kRtNone) return kRtNone;
     cl.sfirst[n] = q;
